@@ -19,10 +19,16 @@ Launch: `python bench.py --gpus N --steps K --warmup W`.  Under torch.distribute
 driver's way for N > 1) every rank reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*; WITHOUT it
 (`WORLD_SIZE` unset) and N > 1 this process starts the N ranks itself -- fresh child processes,
 started before anything here touches a GPU -- and fails loudly if the node has fewer than N
-devices.  Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by a
-barrier + synchronize on both sides, repeated until 0.5 s of timed work has accumulated
-(--min-time); a block's time is the MAX over ranks; `value` comes from the MEDIAN block, the
-spread is reported next to it.
+devices.  Timing: W warm-up steps, then ONE block of exactly K steps bracketed by a barrier +
+synchronize on both sides (--min-time S repeats the block until S seconds are timed; `value`
+then comes from the MEDIAN block, the spread is reported next to it); a block's time is the
+MAX over ranks.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the
+line.  --full adds what takes runs of its own: the CPU baselines (the reference on the same
+graph and on a 1 M-variable sample), the calibration loop of roofline.secondary
+(tools/sorted_bench / gather_bench --ceiling) and the untimed repeated-inference legs.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md §6 for every field.
 """
@@ -97,8 +103,14 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=["cfg3", "cfg5b"], default="cfg3")
-    ap.add_argument("--min-time", type=float, default=0.5,
-                    help="repeat the timed block of --steps steps until this many seconds are timed")
+    ap.add_argument("--min-time", type=float, default=0.0,
+                    help="repeat the timed block of --steps steps until this many seconds are timed "
+                         "(default: one block, exactly --steps timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the roofline.secondary calibration run and the "
+                         "repeated-inference legs (each --no-* option below still turns its part off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0)")
     ap.add_argument("--max-repeats", type=int, default=200)
     ap.add_argument("--vars-per-gpu", type=int, default=0,
                     help="override the per-GPU variable count (default 10M at 1 GPU, 12.5M else)")
@@ -270,6 +282,31 @@ def gather_ceiling():
     return None
 
 
+# entries kept of a longer output (a fixed, seeded sample, the same indices in every run):
+# 2^22 f64 weights + 2^20 entries of each per-value / per-variable array = 56 MiB at most
+DUMP_MAX_WEIGHTS = 1 << 22
+DUMP_MAX_ENTRIES = 1 << 20
+DUMP_SEED = 20260103
+
+
+def dump_outputs(sampler, out_dir):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the learned
+    weights, the tallies behind the marginals and the two chains' assignments -- as
+    out_dir/<name>.npy (float64; the assignments, small integers, as float32)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    t, n = sampler.tallies()
+    outputs = (("weights", sampler.weights, np.float64, DUMP_MAX_WEIGHTS),
+               ("tallies", t, np.float64, DUMP_MAX_ENTRIES),
+               ("tally_counts", n, np.float64, DUMP_MAX_ENTRIES),
+               ("assignments_free", sampler.assignments("free"), np.float32, DUMP_MAX_ENTRIES),
+               ("assignments_evid", sampler.assignments("evid"), np.float32, DUMP_MAX_ENTRIES))
+    for name, a, dt, cap in outputs:
+        if len(a) > cap:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(dt))
+
+
 # --------------------------------------------------------------------------- one rank
 def main():
     args = parse_args()
@@ -366,7 +403,7 @@ def main():
             % (wl, V, W, graph.info.num_tiles, graph.info.num_colors, raw.num_ghost_variables,
                graph.info.device_bytes / 1e9, time.time() - t0))
     # (kept for the like-for-like CPU baseline: the reference runs on this very graph)
-    raw_full = raw if (n_gpus == 1 and wl == "cfg3" and not args.no_cpu_baseline) else None
+    raw_full = raw if (args.full and n_gpus == 1 and wl == "cfg3" and not args.no_cpu_baseline) else None
     del raw
     engine = HipEngine(sampler)
     halo = None
@@ -429,11 +466,13 @@ def main():
     ms_l, nl_l, ns_l = sampler.kernel_time("learn")
     ms_p, nl_p, ns_p = sampler.kernel_time("pull")
     comm = engine.comm_timing.drain() if engine.comm_timing is not None else {}
-    # outside the timed region: inference sweeps that FOLLOW EACH OTHER on unchanged weights
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sampler, args.dump_outputs)
+    # (--full) outside the timed region: inference sweeps that FOLLOW EACH OTHER on unchanged weights
     # (what `dw gibbs -i N` runs) stream tabulated potential terms instead of gathering
     # weights; the step above alternates learning and inference and never gets there
     ms_r = nl_r = ns_r = 0
-    if not args.no_repeat_infer and halo is None:
+    if args.full and not args.no_repeat_infer and halo is None:
         sampler.kernel_time_reset(True)
         for _ in range(6):
             engine.sample()
@@ -447,7 +486,7 @@ def main():
     # (dwx_sample_n_async); aside too, never part of `value`
     ms_m = ns_m = 0
     N_MULTI = 100
-    if not args.no_repeat_infer and halo is None and hasattr(engine, "sample_n"):
+    if args.full and not args.no_repeat_infer and halo is None and hasattr(engine, "sample_n"):
         engine.sample_n(N_MULTI); engine.wait()
         sampler.kernel_time_reset(True)
         engine.sample_n(N_MULTI)
@@ -543,7 +582,7 @@ def main():
         # on denser graphs (it read 1.14 at 100 M variables).
         if wl == "cfg3" and kern == "sorted_sweep_kernel":
             recs = RECORDS_PER_VAR[wl] * units
-            peak = None if args.no_gather_ceiling else sorted_ceiling()
+            peak = None if (args.no_gather_ceiling or not args.full) else sorted_ceiling()
             committed = 3.5e11      # profiles/r03/sorted_bench.jsonl: 16 384 variables, 1024 threads, 1 per CU
             r_ach = recs / sweep_s
             roofline["secondary"] = {"bound": "cu_vector_memory", "what": "weight-sorted 8-byte record stream + "
@@ -555,7 +594,7 @@ def main():
                                      "note": "a micro-benchmark of the same loop, a diagnostic and not a bound"}
         elif wl == "cfg3":
             gathers = RECORDS_PER_VAR[wl] * units
-            peak = None if args.no_gather_ceiling else gather_ceiling()
+            peak = None if (args.no_gather_ceiling or not args.full) else gather_ceiling()
             committed = 1.874e11    # profiles/r02/gather_bench.jsonl: stream mode, 4 MB, 3 waves/SIMD
             g_ach = gathers / sweep_s
             roofline["secondary"] = {"bound": "l2_req", "what": "random 4-byte weight gathers (one 128-byte L2 "
@@ -570,7 +609,7 @@ def main():
             "value": total_vars / elapsed,
             "unit": "variables/s",
             "n_gpus": n_gpus, "rccl_ranks": rccl_ranks if use_dist else None, "backend": backend if use_dist else None,
-            "steps": args.steps, "warmup": args.warmup,
+            "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": 1e3 * elapsed / args.steps,
             "repeats": repeats,
             "ms_per_step_min": 1e3 * min(blocks) / args.steps, "ms_per_step_max": 1e3 * max(blocks) / args.steps,
@@ -620,7 +659,7 @@ def main():
             out["allreduce_bytes_per_step"] = ar[2] / n_steps_timed
             out["halo_ms_per_step"] = hl[0] / n_steps_timed
             out["halo_bytes_per_step"] = hl[2] / n_steps_timed
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             # the reference on the SAME graph the GPU number is quoted on (like for like), and on
             # the bounded 1 M-variable sample of the same generator earlier rounds reported
             for key, make, smaller in (

@@ -37,7 +37,7 @@ def _check(out, n_gpus):
 @pytest.mark.gpu
 def test_bench_single_process_small():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                        "--vars-per-gpu", "200000", "--cpu-sample-vars", "20000"],
+                        "--vars-per-gpu", "200000", "--cpu-sample-vars", "20000", "--full", "--min-time", "0.5"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _check(r.stdout, 1)
@@ -55,6 +55,39 @@ def test_bench_single_process_small():
     assert d["roofline"]["traffic"] is None      # (not the profiled size: no PMC figure, the layout model speaks)
     # (200k variables: a block of 3 steps takes 0.2 ms, so the repeat cap ends the run, not --min-time)
     assert d["rccl_ranks"] is None and (d["timed_seconds"] >= 0.4 or d["repeats"] == 200)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_exactly_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full) times exactly --steps steps once and runs none of the extras;
+    --dump-outputs writes the last step's outputs, float32 / float64, within 64 MB (1.5 M
+    variables: the per-variable arrays are sampled), identical from run to run."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
+                            "--vars-per-gpu", "1500000", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = _check(r.stdout, 1)
+        assert line["steps"] == 4 and line["repeats"] == 1 and line["full"] is False
+        assert abs(line["timed_seconds"] - 4 * line["ms_per_step"] * 1e-3) < 1e-9
+        assert "cpu_baseline" not in line and line["infer_repeat_kernel_ms"] is None
+        assert "committed" in line["roofline"]["secondary"]["reference_loop_source"]
+        files = sorted(os.listdir(d))
+        assert files == sorted(["weights.npy", "tallies.npy", "tally_counts.npy",
+                                "assignments_free.npy", "assignments_evid.npy"])
+        assert sum(os.path.getsize(d / f) for f in files) <= 64_000_000
+        out = {f: np.load(d / f) for f in files}
+        for f, a in out.items():
+            assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f
+        assert len(out["weights.npy"]) == line["config"]["weights"]
+        assert len(out["assignments_free.npy"]) == 1 << 20
+        assert out["tally_counts.npy"].max() > 0
+        dumps.append(out)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 @pytest.mark.gpu

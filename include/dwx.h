@@ -395,7 +395,11 @@ int dwx_stream(dwx_sampler *s, void **stream);
  * than the launches it replaces: sampler_amd/csrc/persist_kernels.h); 5 = no time: launches = sweeps =
  * the split learning sweeps that ran with ONE launch per mini-batch -- the update of a mini-batch as the
  * prologue of the next one's sweep kernel (all-unary graphs with at most 1024 weights and no
- * degree-binned variable; the default for them, DWX_NO_MERGED_APPLY=1 at dwx_sampler_create disables it). */
+ * degree-binned variable; the default for them, DWX_NO_MERGED_APPLY=1 at dwx_sampler_create disables it); 6 = no
+ * time: launches = the weight-sorted super-tiles of learning sweeps that took their potentials from the
+ * potential cache instead of streaming their records, sweeps = the learning sweeps that read it, since the
+ * sampler was created (all-unary graphs with weight-sorted learning sweeps, an un-split learning sweep right
+ * after an inference sweep on the same weights; DWX_NO_POT_CACHE=1 at the first inference sweep disables it). */
 int dwx_kernel_time(dwx_sampler *s, int kind, double *ms, uint64_t *launches, uint64_t *sweeps);
 int dwx_kernel_time_reset(dwx_sampler *s, int enable);
 

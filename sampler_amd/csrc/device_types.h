@@ -265,6 +265,12 @@ struct KernelParams {
   uint32_t lds_agg_off;       // byte offset of the per-workgroup gradient accumulators
                               // (int64[2W], learning kernel, only when W <= LDS_AGG_MAX_W), else 0
   uint32_t n_sweeps;          // MULTI builds of the inference sweep: sweeps [sweep, sweep + n_sweeps) in one launch
+  // potential cache (sorted_sweep_kernel): [V] fixed-point sums pp - pn by device position, or
+  // null.  Inference: every drawn variable's sum is stored.  Learning: the super-tiles lying wholly inside
+  // variables [pot_v0, pot_v1) take their sums from it instead of streaming their records.
+  long long *pot;
+  uint32_t pot_v0, pot_v1;
+  uint32_t super_rot;         // sorted_sweep_kernel: workgroup b takes super-tile (b + super_rot) mod n_supers
 };
 
 // A split learning sweep of a few-weights graph as ONE persistent launch (persist_learn8_kernel,

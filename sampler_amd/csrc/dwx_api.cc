@@ -161,6 +161,16 @@ struct dwx_sampler {
   // tabulated potential terms of the pre-signed records (inference with unchanged weights)
   EdgeTerms *d_terms = nullptr;
   int terms_state = 0;          // 0 weights changed since / 1 one inference sweep ran on them / 2 table valid
+  // potential cache: on an all-unary graph a variable's pp - pn depends on the weights
+  // only, so the learning sweep that follows an inference sweep on the same weights takes the query
+  // variables' sums the inference sweep summed instead of streaming their records again
+  long long *d_pot = nullptr;       // [V] fixed-point sums by device position (allocated on first use)
+  int pot_alloc = 0;                // 0 not tried yet, 1 d_pot allocated, -1 no cache (not eligible, DWX_NO_POT_CACHE, no memory)
+  std::vector<uint8_t> pot_valid;   // [launches] one sweep stored every query tile's sum, no weight changed since
+  bool pot_wanted = false;          // a learning sweep has followed an inference sweep: inference sweeps store
+  bool last_infer = false;          // the last sweep enqueued was an inference sweep
+  bool pot_query_first = false;     // DWX_POT_QUERY_FIRST: a learning launch runs its cached super-tiles first (A/B)
+  uint64_t pot_supers = 0, pot_sweeps = 0;   // super-tiles / learning sweeps served from the cache
   bool has_simple_tiles = false;
   // pull-based gradient (TILE_PULL tiles)
   unsigned long long *d_delta = nullptr;
@@ -258,6 +268,7 @@ struct dwx_sampler {
     rt::dfree(d_grad32); rt::dfree(d_pack_bad);
     rt::dfree(d_edges); rt::dfree(d_edges8); rt::dfree(d_vifs); rt::dfree(d_assign_free); rt::dfree(d_assign_evid);
     rt::dfree(d_tally); rt::dfree(d_weights); rt::dfree(d_w32); rt::dfree(d_w_init); rt::dfree(d_terms); rt::dfree(d_delta);
+    rt::dfree(d_pot);
     rt::dfree(d_w_fixed); rt::dfree(d_grad); rt::dfree(d_persist_rows); rt::dfree(d_persist_bar);
     rt::dfree(d_gbuf[1]); rt::dfree(d_gbuf[2]); rt::dfree(d_wbuf64[0]); rt::dfree(d_wbuf64[1]); rt::dfree(d_wbuf32[0]); rt::dfree(d_wbuf32[1]);
     for (int i = 0; i < 2; ++i) { if (side[i]) rt::stream_destroy(side[i]); if (ev_join[i]) rt::event_destroy(ev_join[i]); }
@@ -279,11 +290,20 @@ struct dwx_halo {
 };
 
 namespace {
+// d_w32 is about to change: the terms table and the potential cache are stale from here on
+void weights_change(dwx_sampler *s) {
+  s->terms_state = 0;
+  std::fill(s->pot_valid.begin(), s->pot_valid.end(), (uint8_t)0);
+}
+
 // launch the sweep kernel (+ the oversized-variable kernel) over tiles [t0, t1) of launch l
 // multi (inference of a graph without degree-binned variables): P.n_sweeps sweeps per launch
+// covered (if given): the end of the gap-free run of weight-sorted super-tiles that starts at t0 (t0: none)
 template <bool LEARN>
-uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, uint32_t t1, const bool multi = false) {
+uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, uint32_t t1, const bool multi = false,
+                      uint32_t *covered = nullptr) {
   const CompiledGraph &c = *s->cg;
+  if (covered) *covered = t0;
   if (t1 <= t0) return 0;
   uint32_t launches = 0;
   P.tile_begin = t0;
@@ -377,8 +397,9 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
   // the tiles before, between and behind them: the tile sweep.
   bool used_sorted = false;
   if (s->d_supers && !P.edge_terms && !multi && (!LEARN || (s->sorted_learn && !(P.flags & (OPT_NO_PULL | OPT_DYNAMIC_T))))) {
-    // (a chunk of a split learning sweep: the plan level's own layout, cut along the chunks)
-    const dwx_sampler::Level *lv = (LEARN && s->plan_level && s->plan_level->d_supers) ? s->plan_level : nullptr;
+    // (a chunk of a split learning sweep: the plan level's own layout, cut along the chunks; a learning
+    // launch on the potential cache: the default layout, whose super-tiles end at the query tiles' end)
+    const dwx_sampler::Level *lv = (LEARN && !P.pot && s->plan_level && s->plan_level->d_supers) ? s->plan_level : nullptr;
     const std::vector<SuperTile> &sv = lv ? lv->sorted_supers : c.supers;
     const SuperTile *d_sv = lv ? lv->d_supers : s->d_supers;
     const SortRec8 *d_sr = lv ? lv->d_sorted : s->d_sorted;
@@ -403,9 +424,22 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
     }
     if (!runs.empty() && runs.size() <= 8) {
       used_sorted = true;
+      if (covered && sv[runs[0].a].tile0 == t0) *covered = sv[runs[0].b - 1].tile0 + sv[runs[0].b - 1].ntiles;
       uint32_t cursor = t0;
       for (const Run &r : runs) {
         launch_lane_tiles(cursor, sv[r.a].tile0);
+        // learning on the potential cache: the cached super-tiles (the query tiles, at the head of the run)
+        // cost a fraction of the streamed ones; the launch starts behind them so that they fill the tail
+        // of the streamed super-tiles' last round (DWX_POT_QUERY_FIRST: in tile order)
+        P.super_rot = 0;
+        if (LEARN && P.pot) {
+          uint32_t n_cached = 0;
+          for (size_t i = r.a; i < r.b; ++i)
+            if (sv[i].v0 >= P.pot_v0 && sv[i].v0 + sv[i].nv <= P.pot_v1) ++n_cached;
+          s->pot_supers += n_cached;
+          if (!s->pot_query_first && n_cached < r.b - r.a && sv[r.a].v0 >= P.pot_v0 && sv[r.a].v0 + sv[r.a].nv <= P.pot_v1)
+            P.super_rot = n_cached;   // (cached ones lead the run: the range is the launch's first tiles)
+        }
         // (one distinct d: the UNI build keeps it in a scalar register; DWX_NO_SORT_UNI: A/B knob)
         if (s->n_sort_dvals == 2 && !s->no_sort_uni)
           rt::launch(sorted_sweep_kernel<LEARN, true>, (unsigned)(r.b - r.a), SORT_THREADS, s->lds_sorted, s->stream, P,
@@ -416,6 +450,7 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
                      (const SuperTile *)(d_sv + r.a), (uint32_t)(r.b - r.a), d_sr,
                      (const double *)s->d_sort_dvals, s->n_sort_dvals);
         ++launches;
+        P.super_rot = 0;
         cursor = sv[r.b - 1].tile0 + sv[r.b - 1].ntiles;
       }
       launch_lane_tiles(cursor, t1);
@@ -497,12 +532,35 @@ void enqueue_inference_multi(dwx_sampler *s, uint32_t n) {
   s->sweep += n;
 }
 
+// The potential cache's array, allocated on first use: compact-record graphs whose learning sweeps take
+// the weight-sorted super-tiles.  false: this sampler runs without it (not eligible, DWX_NO_POT_CACHE, or
+// no device memory for it even after the OOM hook).
+bool pot_cache_ready(dwx_sampler *s) {
+  if (s->pot_alloc == 0) {
+    const CompiledGraph &c = *s->cg;
+    s->pot_alloc = -1;
+    if (s->rec8 && s->d_supers && s->sorted_learn && !getenv("DWX_NO_POT_CACHE")) {
+#ifdef DWX_EMU
+      s->d_pot = (long long *)rt::dmalloc(c.V * sizeof(long long));
+#else
+      s->d_pot = (long long *)rt::try_dmalloc(c.V * sizeof(long long));
+#endif
+      if (s->d_pot) {
+        s->pot_alloc = 1;
+        s->pot_valid.assign(c.launch_tile.size(), 0);
+      }
+    }
+  }
+  return s->pot_alloc > 0;
+}
+
 // one inference sweep (GibbsSampler::sample)
 void enqueue_inference(dwx_sampler *s) {
   const CompiledGraph &c = *s->cg;
   rt::set_device(s->device);
   KernelParams P = s->base;
   P.sweep = s->sweep;
+  s->last_infer = true;
   // The second consecutive inference sweep on the same weights tabulates the pre-signed
   // records' potential terms (one extra pass, about the cost of a sweep); from then on
   // sweeps stream the table and gather no weights.  (Not on the first one: learning and
@@ -522,6 +580,9 @@ void enqueue_inference(dwx_sampler *s) {
   }
   P.edge_terms = s->terms_state == 2 ? s->d_terms : nullptr;
   if (s->terms_state == 0) s->terms_state = 1;
+  // the potential cache is stored once a learning sweep is known to follow inference sweeps (on a
+  // sampler that only infers, it would be bandwidth spent for nothing -- the rule of the terms table)
+  P.pot = (s->pot_wanted && !P.edge_terms && pot_cache_ready(s)) ? s->d_pot : nullptr;
   TimedSpan sp{};
   if (s->timing) {
     sp.a = rt::event_create(); sp.b = rt::event_create(); sp.c = rt::event_create(); sp.kind = 0;
@@ -531,7 +592,11 @@ void enqueue_inference(dwx_sampler *s) {
   for (size_t l = 0; l + 1 < c.launch_off.size(); ++l) {
     // only the query variables' tiles unless --sample_evidence (src/gibbs_sampler.h:157)
     const uint32_t t1 = s->opts.sample_evidence ? c.launch_tile[l + 1] : c.launch_query_tile_end[l];
-    launches += launch_tiles<false>(s, P, l, c.launch_tile[l], t1);
+    uint32_t covered = 0;
+    launches += launch_tiles<false>(s, P, l, c.launch_tile[l], t1, false, &covered);
+    // valid for launch l only if sorted_sweep_kernel stored the sum of EVERY query tile (none took the
+    // tile sweep, the terms table or a degree-bin kernel)
+    if (P.pot && c.launch_query_tile_end[l] > c.launch_tile[l] && covered >= c.launch_query_tile_end[l]) s->pot_valid[l] = 1;
   }
   if (s->timing) {
     rt::event_record(sp.b, s->stream);
@@ -1353,6 +1418,19 @@ void enqueue_learn_chunk(dwx_sampler *s, uint32_t chunk) {
   // a split sweep without per-chunk tables falls back to per-record atomics and counts
   const bool fast = L.fast && !(split && s->plan_force_dynamic);
   if (split && !fast) P.flags |= OPT_DYNAMIC_T | OPT_NO_PULL;
+  // an un-split sweep on weights the last inference sweep summed: its query super-tiles read the cache
+  if (chunk == 0) {
+    if (s->last_infer) s->pot_wanted = true;
+    s->last_infer = false;
+  }
+  const uint32_t l = ch.launch;
+  if (!split && s->pot_alloc > 0 && l < s->pot_valid.size() && s->pot_valid[l]) {
+    const CompiledGraph &c = *s->cg;
+    P.pot = s->d_pot;
+    P.pot_v0 = c.tile_v[c.launch_tile[l]];
+    P.pot_v1 = c.tile_v[c.launch_query_tile_end[l]];
+    if (chunk == 0) ++s->pot_sweeps;
+  }
   TimedSpan sp{};
   const bool timing = s->timing;
   if (timing) {
@@ -1423,7 +1501,7 @@ void enqueue_learn_chunk(dwx_sampler *s, uint32_t chunk) {
 
 void enqueue_apply(dwx_sampler *s) {
   rt::set_device(s->device);
-  s->terms_state = 0;   // the weights change
+  weights_change(s);
   const uint32_t W = (uint32_t)s->cg->W;
   if (!W) return;
   const unsigned grid = std::min<unsigned>((W + BLOCK_THREADS - 1) / BLOCK_THREADS, 2048u);
@@ -1569,7 +1647,7 @@ bool enqueue_merged_sweep(dwx_sampler *s) {
                s->d_gbuf[last % 3], ts, ts + W, W, s->plan_eta, s->opts.reg_param, (int)(s->opts.regularization == 1), w_in,
                last ? s->d_gbuf[(last - 1) % 3] : (long long *)nullptr);
   }
-  s->terms_state = 0;
+  weights_change(s);
   ++s->merged_sweeps;
   return true;
 }
@@ -1627,7 +1705,7 @@ bool enqueue_persistent_sweep(dwx_sampler *s) {
     sp.launches = 1; sp.has_pull = false; sp.new_sweep = true;
     s->spans.push_back(sp);
   }
-  s->terms_state = 0;               // the weights change
+  weights_change(s);
   s->cur_chunk = n - 1;
   s->persist_check_pending = true;
   ++s->persist_launches;
@@ -1844,6 +1922,7 @@ int dwx_sampler_create(const dwx_graph *g, const dwx_options *opts, dwx_sampler 
       rt::allow_dynamic_lds(sorted_sweep_kernel<false, true>, s->lds_sorted);
       rt::allow_dynamic_lds(sorted_sweep_kernel<true, true>, s->lds_sorted);
       s->no_sort_uni = getenv("DWX_NO_SORT_UNI") != nullptr;
+      s->pot_query_first = getenv("DWX_POT_QUERY_FIRST") != nullptr;
     }
     {
       // the batched walks load a factor's first entries branch-free (a unary record reads entry
@@ -2344,7 +2423,7 @@ int dwx_set_weights(dwx_sampler *s, const double *in) {
   return guarded([&]() {
     rt::set_device(s->device);
     const uint32_t W = (uint32_t)s->cg->W;
-    s->terms_state = 0;
+    weights_change(s);
     rt::h2d(s->d_weights, in, (size_t)W * 8, s->stream);
     if (W) {
       const unsigned grid = std::min<unsigned>((W + BLOCK_THREADS - 1) / BLOCK_THREADS, 2048u);
@@ -2362,7 +2441,7 @@ int dwx_average_weights_async(dwx_sampler *s, uint32_t n_replicas) {
     rt::set_device(s->device);
     const uint32_t W = (uint32_t)s->cg->W;
     if (!W) return;
-    s->terms_state = 0;
+    weights_change(s);
     if (!s->d_w_init) {
       s->d_w_init = upload(s->cg->w_init, s->stream);
       rt::stream_sync(s->stream);
@@ -2572,7 +2651,13 @@ int dwx_kernel_time_reset(dwx_sampler *s, int enable) {
 }
 
 int dwx_kernel_time(dwx_sampler *s, int kind, double *ms, uint64_t *launches, uint64_t *sweeps) {
-  if (!s || kind < 0 || kind > 5) return fail(DWX_E_INVALID, "bad argument");
+  if (!s || kind < 0 || kind > 6) return fail(DWX_E_INVALID, "bad argument");
+  if (kind == 6) {   // learning sweeps (and their super-tiles) that took sums from the potential cache
+    if (ms) *ms = 0.0;
+    if (launches) *launches = s->pot_supers;
+    if (sweeps) *sweeps = s->pot_sweeps;
+    return DWX_OK;
+  }
   if (kind == 5) {   // split learning sweeps run with one (merged) launch per mini-batch since the sampler was created
     if (ms) *ms = 0.0;
     if (launches) *launches = s->merged_sweeps;

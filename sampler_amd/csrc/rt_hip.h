@@ -61,6 +61,19 @@ inline void *dmalloc(size_t n) {
   DWX_HIP(e);
   return p;
 }
+// (an optional buffer: nullptr instead of an exception when the device is out of memory, the hook tried)
+inline void *try_dmalloc(size_t n) {
+  void *p = nullptr;
+  hipError_t e = hipMalloc(&p, n ? n : 16);
+  if (e != hipSuccess && oom_hook()) {
+    (void)hipGetLastError();
+    int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess) oom_hook()(dev);
+    e = hipMalloc(&p, n ? n : 16);
+  }
+  if (e != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  return p;
+}
 inline void dfree(void *p) { if (p) (void)hipFree(p); }
 // Large uploads go through the library's own pinned staging buffers (two 64 MiB chunks in turn, filled by a
 // few host threads) instead of hipMemcpyAsync on the caller's pageable array.  The runtime's own path is a

@@ -757,9 +757,16 @@ sorted_sweep_kernel(const KernelParams P, const SuperTile *supers, uint32_t n_su
   double *s_d = (double *)(dyn_lds + SUPER_NV_MAX * sizeof(long long) + SORT_TV_SLOTS * sizeof(uint32_t));   // [n_dvals]
   const uint32_t t = threadIdx.x;
   if (blockIdx.x >= n_supers) return;
-  SuperTile S = supers[blockIdx.x];
+  // (P.super_rot: the launch starts at that super-tile and wraps round -- launch_tiles)
+  const uint32_t b = blockIdx.x + P.super_rot;
+  SuperTile S = supers[b < n_supers ? b : b - n_supers];
   S.tile0 = DWX_UNIFORM(S.tile0); S.ntiles = DWX_UNIFORM(S.ntiles); S.v0 = DWX_UNIFORM(S.v0); S.nv = DWX_UNIFORM(S.nv);
   S.lo = DWX_UNIFORM(S.lo); S.hi = DWX_UNIFORM(S.hi); S.nrec = DWX_UNIFORM(S.nrec);
+  // learning, a super-tile of the potential cache's valid range: its sums are those an
+  // inference sweep just stored under the same weights -- no record is streamed (nrec 0: the buffer
+  // loads zero-fill), the draw passes load the sums with the per-variable words
+  const bool cached = LEARN && P.pot && S.v0 >= P.pot_v0 && S.v0 + S.nv <= P.pot_v1;
+  if (cached) S.nrec = 0;
   const SortRec8 *base = recs + (((uint64_t)S.hi << 32) | S.lo);
   SortRec8 rec[SORT_K];
   DWX_LOAD_SORTED_RECORDS(SORT_K, base, S.nrec, 0u, t, rec);
@@ -791,7 +798,7 @@ sorted_sweep_kernel(const KernelParams P, const SuperTile *supers, uint32_t n_su
   // clamped inside the super-tile)
   constexpr uint32_t TPB = SORT_THREADS / BLOCK_THREADS;
   const uint32_t lane = t & (BLOCK_THREADS - 1), sub = t / BLOCK_THREADS;
-  struct Pass { bool have; uint32_t tile, p; bool live; VarPre pre; };
+  struct Pass { bool have; uint32_t tile, p; bool live; VarPre pre; long long sum; };
   auto issue = [&](uint32_t j0) {
     Pass ps;
     ps.have = j0 + sub < S.ntiles;
@@ -801,6 +808,7 @@ sorted_sweep_kernel(const KernelParams P, const SuperTile *supers, uint32_t n_su
     ps.live = ps.have && lane < tnv;
     ps.p = tv0 + (lane < tnv ? lane : tnv - 1u);
     ps.pre = load_var_pre<LEARN>(P, ps.p);
+    ps.sum = cached ? DWX_NT_LOAD(&P.pot[ps.p]) : 0ll;
     return ps;
   };
   Pass nxt = issue(0u);
@@ -812,7 +820,10 @@ sorted_sweep_kernel(const KernelParams P, const SuperTile *supers, uint32_t n_su
     if (ps.live) {
       double A, B;
       philox_uniforms(P.seed, P.vid_offset + ps.pre.orig, P.sweep, A, B);
-      const double x = pot_unfix((long long)s_acc[ps.p - S.v0]);
+      const long long sum = cached ? ps.sum : (long long)s_acc[ps.p - S.v0];
+      // (inference: the sum into the potential cache, one coalesced non-temporal 8-byte store per variable)
+      if (!LEARN && P.pot) DWX_NT_STORE(sum, &P.pot[ps.p]);
+      const double x = pot_unfix(sum);
       TileView T{nullptr, 0u, nullptr, 0u, nullptr, nullptr, nullptr};
       T.presum = &x;
       delta = process_variable<LEARN, W_FIXSUM, true>(P, T, ps.p, ps.pre, A, B, true);

@@ -316,6 +316,26 @@ int dwx_average_weights_async(dwx_sampler *s, uint32_t n_replicas);
  * (src/inference_result.cc:107-127); arrays are in the REFERENCE numbering. */
 int dwx_clear_tallies(dwx_sampler *s);
 int dwx_get_tallies(dwx_sampler *s, uint64_t *tallies, uint64_t *nsamples);
+/* Rao-Blackwellised marginals.  NO reference counterpart: the reference's only estimator counts the drawn
+ * values (sample_single_variable, src/gibbs_sampler.h:160-167; dumped as tally / nsamples,
+ * src/inference_result.cc:211-243).  Every inference draw first computes the exact conditional
+ * P(x_v = d | all other variables) of the variable it samples -- 1 / (1 + exp(pn - pp)) for a boolean
+ * variable (draw_sample, src/gibbs_sampler.h:198-215), exp(pot_d - m) / sum_j exp(pot_j - m), m = max_j
+ * pot_j, for a categorical one (:217-246) -- from the very potentials the draw decides on.  While the switch
+ * is on, every inference sweep (dwx_sample_async, dwx_sample_n_async; never a learning sweep) adds
+ * llrint(2^32 * that probability), evaluated in f64, to an unsigned 64-bit sum per value row for every
+ * variable it samples (the set whose nsamples grows).  sums / 2^32 / nsamples estimates the same marginal
+ * as tallies / nsamples from the same chain (Gelfand & Smith 1990) with a smaller variance wherever a
+ * variable's own evidence is informative; on an all-unary graph it is exact after one sweep.  The integer
+ * sums do not depend on the kernels a graph takes, on dwx_sample_n_async against single sweeps, or on how
+ * a graph without cross-shard factors is split over ranks.  Rows of variables that are not sampled stay 0.
+ *   dwx_rb_enable(s, 1)  allocates and zeroes the sums on first use (8 bytes per value row; DWX_E_NOMEM
+ *                        leaves the sampler usable, switch off); (s, 0) stops accumulating, keeps the sums.
+ *   dwx_get_rb_sums      sums[num_values] and nsamples[num_variables] in the REFERENCE numbering, as
+ *                        dwx_get_tallies (either may be null); DWX_E_INVALID when never enabled.
+ *   dwx_clear_tallies    zeroes them with the tallies; DWX_BUF_RB is the device array. */
+int dwx_rb_enable(dwx_sampler *s, int on);
+int dwx_get_rb_sums(dwx_sampler *s, uint64_t *sums, uint64_t *nsamples);
 /* assignments_free (chain 0) / assignments_evid (chain 1), original variable order */
 int dwx_get_assignments(dwx_sampler *s, int chain, uint64_t *out);
 int dwx_set_assignments(dwx_sampler *s, int chain, const uint64_t *in);
@@ -343,9 +363,12 @@ enum {
                                slowest rank) and sums the table across shards ONCE per
                                batch count (the library caches it per batch count)   */
   DWX_BUF_SORTED_RECORDS = 7,      /* test hooks: the weight-sorted record copy of the graph's default  */
-  DWX_BUF_SORTED_RECORDS_PLAN = 8  /* layout / of the current plan level's own (8 bytes per record;
+  DWX_BUF_SORTED_RECORDS_PLAN = 8, /* layout / of the current plan level's own (8 bytes per record;
                                       null / 0 bytes when there is none): the device build
                                       (device_build.hip) is checked against the host builder's bytes  */
+  DWX_BUF_RB = 9            /* uint64[num_values] in device order, like DWX_BUF_TALLIES: the
+                               Rao-Blackwellised sums (2^-32 fixed point; dwx_rb_enable); null / 0
+                               bytes when never enabled.  Replicas sum it with a 64-bit integer sum  */
 };
 int dwx_device_buffer(dwx_sampler *s, int which, void **dev_ptr, uint64_t *nbytes);
 /* Copy between host memory and a device pointer obtained from dwx_device_buffer /

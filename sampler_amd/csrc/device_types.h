@@ -271,6 +271,10 @@ struct KernelParams {
   long long *pot;
   uint32_t pot_v0, pot_v1;
   uint32_t super_rot;         // sorted_sweep_kernel: workgroup b takes super-tile (b + super_rot) mod n_supers
+  // Rao-Blackwellised marginals (tile_walk.h, rb_*): [R] unsigned 32.32 fixed-point sums of the conditionals
+  // the inference draws decide on, laid out like `tally`; null = off.  Only read by the RB builds of the
+  // inference kernels (last member: no other kernel's argument offsets move).
+  unsigned long long *rb;
 };
 
 // A split learning sweep of a few-weights graph as ONE persistent launch (persist_learn8_kernel,

@@ -42,7 +42,7 @@ const FlagSpec kFlags[] = {
     {"", "regularization", true}, {"q", "quiet", false}, {"", "sample_evidence", false},
     {"", "learn_non_evidence", false}, {"", "noise_aware", false},
     {"", "device", true}, {"", "seed", true}, {"", "step_cap", true}, {"", "plan_layouts", true},
-    {"", "gpus", true}, {"", "devices", true}, {"", "comm", true},
+    {"", "gpus", true}, {"", "devices", true}, {"", "comm", true}, {"", "rao_blackwell", false},
 };
 
 const FlagSpec *find_flag(const std::string &tok) {
@@ -178,6 +178,7 @@ CmdLine parse_cmdline(int argc, const char *const argv[]) {
     else if (n == "step_cap") { if (need_d()) a.step_cap = d; }
     else if (n == "plan_layouts") { if (need_u()) a.plan_layouts = (int)u; }
     else if (n == "gpus") { if (need_u()) a.gpus = (int)u; }
+    else if (n == "rao_blackwell") a.rao_blackwell = true;
     else if (n == "comm") {
       if (val != "rccl" && val != "host") { ++a.num_errors; err << "PARSE ERROR: Argument: --comm\n             must be rccl or host\n"; }
       a.comm = val;
@@ -207,7 +208,9 @@ CmdLine parse_cmdline(int argc, const char *const argv[]) {
 // The stdout banner of `dw gibbs` (a drop-in keeps the format scripts grep for: "# label : value"
 // lines between two rules, src/cmd_parser.cc:272-290), driven by a table: label, value printer.
 std::ostream &operator<<(std::ostream &stream, const CmdLine &args) {
-  struct Row { const char *label; void (*print)(std::ostream &, const CmdLine &); };
+  // (show: null = always; a row of an optional addition appears only when its flag is given, so that a run
+  // without the flag keeps the banner's bytes)
+  struct Row { const char *label; void (*print)(std::ostream &, const CmdLine &); bool (*show)(const CmdLine &) = nullptr; };
   // (file lists print as "[a, b]", nothing when empty)
 #define DWX_ROW_LIST(label, field) {label, [](std::ostream &o, const CmdLine &a) { \
     for (size_t i = 0; i < a.field.size(); ++i) o << (i ? ", " : "[") << a.field[i]; \
@@ -233,6 +236,7 @@ std::ostream &operator<<(std::ostream &stream, const CmdLine &args) {
       // additions of this build
       DWX_ROW("device (HIP)", device),
       DWX_ROW("seed", seed),
+      {"rao_blackwell", [](std::ostream &o, const CmdLine &a) { o << a.rao_blackwell; }, [](const CmdLine &a) { return a.rao_blackwell; }},
   };
 #undef DWX_ROW
 #undef DWX_ROW_LIST
@@ -240,6 +244,7 @@ std::ostream &operator<<(std::ostream &stream, const CmdLine &args) {
   const std::string title = "GIBBS SAMPLING";
   stream << std::string(17, '#') << title << std::string(17, '#') << std::endl;
   for (const Row &r : rows) {
+    if (r.show && !r.show(args)) continue;
     std::string label = r.label;
     label.resize(19, ' ');
     stream << "# " << label << ": ";
@@ -821,8 +826,12 @@ inline void append_line(std::string &s, uint64_t a, uint64_t b, double x) {
   s.append(tmp, (size_t)snprintf(tmp, sizeof tmp, "%llu %llu %g\n", (unsigned long long)a, (unsigned long long)b, x));
 }
 // "<id> <value> <tally / nsamples>\n"
-inline void append_marginal(std::string &s, const RatioStrings &rs, uint64_t id, uint64_t value, uint64_t tally, uint64_t nsamples) {
-  if (nsamples == rs.n && rs.n && tally <= rs.n) {
+// (rb: `tally` is a 32.32 fixed-point sum of conditionals, dw::marginal_value)
+inline void append_marginal(std::string &s, const RatioStrings &rs, uint64_t id, uint64_t value, uint64_t tally, uint64_t nsamples,
+                            bool rb = false) {
+  if (rb) {
+    append_line(s, id, value, marginal_value(tally, nsamples, true));
+  } else if (nsamples == rs.n && rs.n && tally <= rs.n) {
     append_u64(s, id); s.push_back(' '); append_u64(s, value); s.push_back(' ');
     s.append(rs.str[tally]); s.push_back('\n');
   } else {
@@ -848,17 +857,17 @@ void dump_weights_to_file(const std::string &path, const std::vector<double> &w)
 
 void dump_marginals_to_file(const std::string &path, const LoadedGraph &g, bool sample_evidence,
                             const uint64_t *var_val_base, const uint64_t *value_sparse,
-                            const uint64_t *tallies, const uint64_t *nsamples) {
+                            const uint64_t *tallies, const uint64_t *nsamples, bool rao_blackwell) {
   RatioStrings rs;
-  rs.build(common_nsamples(g, sample_evidence, nsamples, g.n_variables));
+  if (!rao_blackwell) rs.build(common_nsamples(g, sample_evidence, nsamples, g.n_variables));
   dump_parallel_to_file(path, g.n_variables, [&](uint64_t v, std::string &s) {
     if (g.var_role[v] >= 1 && !sample_evidence) return;
     const uint64_t b = var_val_base[v];
     if (g.var_dtype[v] == 0) {
-      append_marginal(s, rs, v, (uint64_t)1, tallies[b], nsamples[v]);
+      append_marginal(s, rs, v, (uint64_t)1, tallies[b], nsamples[v], rao_blackwell);
     } else {
       for (uint64_t j = 0; j < g.var_cardinality[v]; ++j)
-        append_marginal(s, rs, v, value_sparse[b + j], tallies[b + j], nsamples[v]);
+        append_marginal(s, rs, v, value_sparse[b + j], tallies[b + j], nsamples[v], rao_blackwell);
     }
   });
 }
@@ -866,18 +875,19 @@ void dump_marginals_to_file(const std::string &path, const LoadedGraph &g, bool 
 // src/inference_result.cc:211-243
 void dump_marginals_in_text(std::ostream &o, const LoadedGraph &g, bool sample_evidence,
                             const uint64_t *var_val_base, const uint64_t *value_sparse,
-                            const uint64_t *tallies, const uint64_t *nsamples, uint64_t id_offset, uint64_t n_vars) {
+                            const uint64_t *tallies, const uint64_t *nsamples, uint64_t id_offset, uint64_t n_vars,
+                            bool rao_blackwell) {
   const uint64_t nv = std::min<uint64_t>(g.n_variables, n_vars);
   RatioStrings rs;
-  rs.build(common_nsamples(g, sample_evidence, nsamples, nv));
+  if (!rao_blackwell) rs.build(common_nsamples(g, sample_evidence, nsamples, nv));
   dump_parallel(o, nv, [&](uint64_t v, std::string &s) {
     if (g.var_role[v] >= 1 && !sample_evidence) return;
     const uint64_t b = var_val_base[v];
     if (g.var_dtype[v] == 0) {
-      append_marginal(s, rs, v + id_offset, (uint64_t)1, tallies[b], nsamples[v]);
+      append_marginal(s, rs, v + id_offset, (uint64_t)1, tallies[b], nsamples[v], rao_blackwell);
     } else {
       for (uint64_t j = 0; j < g.var_cardinality[v]; ++j)
-        append_marginal(s, rs, v + id_offset, value_sparse[b + j], tallies[b + j], nsamples[v]);
+        append_marginal(s, rs, v + id_offset, value_sparse[b + j], tallies[b + j], nsamples[v], rao_blackwell);
     }
   });
 }
@@ -1081,6 +1091,8 @@ int gibbs(const CmdLine &args) {
     phase("dump weights");
     // ---- DimmWitted::inference (src/dimmwitted.cc:121-160)
     t_total = now();
+    // --rao_blackwell: the inference sweeps also sum the conditionals their draws decide on (include/dwx.h)
+    if (args.rao_blackwell) ok(dwx_rb_enable(sampler, 1));
     ok(dwx_clear_tallies(sampler));
     for (uint64_t e = 0; e < args.n_inference_epoch; ++e) {
       if (progress) {
@@ -1107,7 +1119,10 @@ int gibbs(const CmdLine &args) {
       // (uninitialised, first touched by the library's parallel fills: zero-filling 3.2 GB of vectors on one
       // thread was 0.3 s at config 5's size; every entry is written -- one GPU owns every variable)
       dwx::RawArray<uint64_t> tallies(info.num_values), nsamples(V), base(V), sparse(info.num_values);
-      ok(dwx_get_tallies(sampler, tallies.data(), nsamples.data()));
+      // (with --rao_blackwell `tallies` holds the 32.32 fixed-point sums: every number below is marginal_value's)
+      const bool rb = args.rao_blackwell;
+      if (rb) ok(dwx_get_rb_sums(sampler, tallies.data(), nsamples.data()));
+      else ok(dwx_get_tallies(sampler, tallies.data(), nsamples.data()));
       ok(dwx_graph_get_values(graph, base.data(), sparse.data()));
       auto sampled = [&](uint64_t v) { return lg.var_role[v] < 1 || args.should_sample_evidence; };
       if (progress) {
@@ -1122,7 +1137,7 @@ int gibbs(const CmdLine &args) {
           const uint64_t n = lg.var_dtype[v] == 0 ? 1 : lg.var_cardinality[v];
           for (uint64_t j = 0; j < n; ++j)
             std::cout << "      @ " << (lg.var_dtype[v] == 0 ? 1 : sparse[base[v] + j]) << " -> EXP="
-                      << 1.0 * tallies[base[v] + j] / nsamples[v] << std::endl;
+                      << marginal_value(tallies[base[v] + j], nsamples[v], rb) << std::endl;
           if (ct % 10 == 0) break;
         }
         std::cout << "   ..." << std::endl;
@@ -1130,7 +1145,7 @@ int gibbs(const CmdLine &args) {
       std::string fn = args.output_folder + "/inference_result.out.text";
       std::cout << "DUMPING... TEXT    : " << fn << std::endl;
       phase("dwx_get_tallies");
-      dump_marginals_to_file(fn, lg, args.should_sample_evidence, base.data(), sparse.data(), tallies.data(), nsamples.data());
+      dump_marginals_to_file(fn, lg, args.should_sample_evidence, base.data(), sparse.data(), tallies.data(), nsamples.data(), rb);
       phase("dump marginals");
       if (progress) {
         // the reference's closing calibration table (InferenceResult::show_marginal_histogram,
@@ -1142,7 +1157,7 @@ int gibbs(const CmdLine &args) {
           if (!sampled(v) || nsamples[v] == 0) continue;
           const uint64_t rows = lg.var_dtype[v] == 0 ? 1 : lg.var_cardinality[v];
           for (uint64_t k = 0; k < rows; ++k) {
-            const double p = (double)tallies[base[v] + k] / (double)nsamples[v];
+            const double p = rb ? marginal_value(tallies[base[v] + k], nsamples[v], true) : (double)tallies[base[v] + k] / (double)nsamples[v];
             ++per_bin[std::min(kBins - 1, (size_t)(p * kBins))];
           }
         }

@@ -43,6 +43,7 @@ struct CmdLine {
   int gpus = 0;                 // --gpus N: variable-block shards over N GPUs (dw_multi.h)
   std::vector<int> devices;     // --devices a,b,...: the ranks' HIP devices (default 0..N-1)
   std::string comm = "rccl";    // --comm rccl | host (host-staged sums: a test stand-in)
+  bool rao_blackwell = false;   // --rao_blackwell: the marginals are the Rao-Blackwellised estimate (dwx_rb_enable)
   int num_errors = 0;
   std::string error_text;
 };
@@ -83,13 +84,18 @@ void dump_weights_in_text(std::ostream &o, const std::vector<double> &w);
 void dump_marginals_in_text(std::ostream &o, const LoadedGraph &g, bool sample_evidence,
                             const uint64_t *var_val_base, const uint64_t *value_sparse,
                             const uint64_t *tallies, const uint64_t *nsamples,
-                            uint64_t id_offset = 0, uint64_t n_vars = ~0ull);   // (a shard: local ids + offset, owned only)
+                            uint64_t id_offset = 0, uint64_t n_vars = ~0ull,    // (a shard: local ids + offset, owned only)
+                            bool rao_blackwell = false);
+// --rao_blackwell: `tallies` holds dwx_get_rb_sums' 32.32 fixed-point sums instead of counts; same rows, same format
+inline double marginal_value(uint64_t tally, uint64_t nsamples, bool rao_blackwell) {
+  return rao_blackwell ? (double)tally / 4294967296.0 / (double)nsamples : 1.0 * tally / nsamples;
+}
 
 // the same two dumps straight into a file (the single-GPU `dw gibbs`)
 void dump_weights_to_file(const std::string &path, const std::vector<double> &w);
 void dump_marginals_to_file(const std::string &path, const LoadedGraph &g, bool sample_evidence,
                             const uint64_t *var_val_base, const uint64_t *value_sparse,
-                            const uint64_t *tallies, const uint64_t *nsamples);
+                            const uint64_t *tallies, const uint64_t *nsamples, bool rao_blackwell = false);
 
 // graph-compile options of a run (dw_cli.cc: the weight order of the variables only for long runs)
 dwx_compile_opts compile_opts_for(const CmdLine &args);

@@ -645,6 +645,7 @@ void Rank::inference() {
   const uint64_t rounds = sh_.replicas ? (args_.n_inference_epoch + n - 1) / n : args_.n_inference_epoch;
   const uint64_t per_round = sh_.replicas ? n : 1;
   double t_total = now();
+  if (args_.rao_blackwell) ok(dwx_rb_enable(s_, 1));     // (--rao_blackwell: include/dwx.h)
   ok(dwx_clear_tallies(s_));
   // quiet and nothing to exchange between the sweeps (replicas; shards without a ghost anywhere):
   // all rounds in one call -- one launch on an all-unary graph (dwx_sample_n_async)
@@ -673,6 +674,15 @@ void Rank::inference() {
   }
   // replicas: aggregate_marginals_from (src/inference_result.cc:113-127) -- sum the copies' tallies
   if (sh_.replicas && rounds && info_.num_values) sh_.comm->allreduce_sum_u32(rank_, s_, d_tallies_, info_.num_values);
+  // ... and their Rao-Blackwellised sums: unsigned 64-bit fixed point on the 64-bit integer sum the gradient
+  // travels on (two's-complement addition: the same bits), normalised by the summed nsamples like the tallies.
+  // (No run with two RCCL ranks has been possible yet: this call is exercised through --comm host only.)
+  if (sh_.replicas && rounds && info_.num_values && args_.rao_blackwell) {
+    void *d_rb = nullptr;
+    uint64_t nb = 0;
+    ok(dwx_device_buffer(s_, DWX_BUF_RB, &d_rb, &nb));
+    sh_.comm->allreduce_sum_i64(rank_, s_, d_rb, nb / 8);
+  }
   ok(dwx_wait(s_));
   sh_.agree->barrier();
   if (root()) std::cout << std::setprecision(6) << "TOTAL INFERENCE TIME: " << now() - t_total << " sec." << std::endl;
@@ -683,7 +693,9 @@ void Rank::collect() {
   if (sh_.replicas && !root()) return;     // every replica holds the summed tallies: one copy is enough
   const uint64_t nv = r.g->n_variables;
   r.tallies.resize(info_.num_values); r.nsamples.resize(nv); r.base.resize(nv); r.sparse.resize(info_.num_values);
-  ok(dwx_get_tallies(s_, r.tallies.data(), r.nsamples.data()));
+  // (--rao_blackwell: the 32.32 fixed-point sums take the tallies' place; shards hand over their own rows alike)
+  if (args_.rao_blackwell) ok(dwx_get_rb_sums(s_, r.tallies.data(), r.nsamples.data()));
+  else ok(dwx_get_tallies(s_, r.tallies.data(), r.nsamples.data()));
   ok(dwx_graph_get_values(graph_, r.base.data(), r.sparse.data()));
   if (sh_.replicas)
     for (auto &x : r.nsamples) x *= (uint64_t)sh_.world;
@@ -899,7 +911,7 @@ int gibbs_multi(const CmdLine &args) {
           const uint64_t k = r0.g->var_dtype[v] == 0 ? 1 : r0.g->var_cardinality[v];
           for (uint64_t j = 0; j < k; ++j)
             std::cout << "      @ " << (r0.g->var_dtype[v] == 0 ? 1 : r0.sparse[r0.base[v] + j]) << " -> EXP="
-                      << 1.0 * r0.tallies[r0.base[v] + j] / r0.nsamples[v] << std::endl;
+                      << marginal_value(r0.tallies[r0.base[v] + j], r0.nsamples[v], args.rao_blackwell) << std::endl;
         }
         std::cout << "   ..." << std::endl;
       }
@@ -909,7 +921,7 @@ int gibbs_multi(const CmdLine &args) {
       for (int r = 0; r < (replicas ? 1 : n); ++r) {
         const Shared::Result &res = sh.results[r];
         dump_marginals_in_text(f, *res.g, args.should_sample_evidence, res.base.data(), res.sparse.data(), res.tallies.data(),
-                               res.nsamples.data(), res.id_offset, res.n_owned);
+                               res.nsamples.data(), res.id_offset, res.n_owned, args.rao_blackwell);
       }
     }
     quick_exit_if_done(0);     // (the result files are written: see dw_cli.cc)

@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <set>
 #include <memory>
 #include <new>
 #include <stdexcept>
@@ -164,6 +165,10 @@ struct dwx_sampler {
   // potential cache: on an all-unary graph a variable's pp - pn depends on the weights
   // only, so the learning sweep that follows an inference sweep on the same weights takes the query
   // variables' sums the inference sweep summed instead of streaming their records again
+  // Rao-Blackwellised marginals (dwx_rb_enable; tile_walk.h rb_*): [R] 32.32 fixed-point sums, device order
+  unsigned long long *d_rb = nullptr;   // allocated by the first enable
+  bool rb_on = false;                   // inference sweeps run the RB builds of their kernels and accumulate
+  std::set<std::pair<const void *, size_t>> rb_lds_allowed;   // RB builds whose dynamic LDS size is already allowed
   long long *d_pot = nullptr;       // [V] fixed-point sums by device position (allocated on first use)
   int pot_alloc = 0;                // 0 not tried yet, 1 d_pot allocated, -1 no cache (not eligible, DWX_NO_POT_CACHE, no memory)
   std::vector<uint8_t> pot_valid;   // [launches] one sweep stored every query tile's sum, no weight changed since
@@ -268,7 +273,7 @@ struct dwx_sampler {
     rt::dfree(d_grad32); rt::dfree(d_pack_bad);
     rt::dfree(d_edges); rt::dfree(d_edges8); rt::dfree(d_vifs); rt::dfree(d_assign_free); rt::dfree(d_assign_evid);
     rt::dfree(d_tally); rt::dfree(d_weights); rt::dfree(d_w32); rt::dfree(d_w_init); rt::dfree(d_terms); rt::dfree(d_delta);
-    rt::dfree(d_pot);
+    rt::dfree(d_pot); rt::dfree(d_rb);
     rt::dfree(d_w_fixed); rt::dfree(d_grad); rt::dfree(d_persist_rows); rt::dfree(d_persist_bar);
     rt::dfree(d_gbuf[1]); rt::dfree(d_gbuf[2]); rt::dfree(d_wbuf64[0]); rt::dfree(d_wbuf64[1]); rt::dfree(d_wbuf32[0]); rt::dfree(d_wbuf32[1]);
     for (int i = 0; i < 2; ++i) { if (side[i]) rt::stream_destroy(side[i]); if (ev_join[i]) rt::event_destroy(ev_join[i]); }
@@ -296,12 +301,21 @@ void weights_change(dwx_sampler *s) {
   std::fill(s->pot_valid.begin(), s->pot_valid.end(), (uint8_t)0);
 }
 
+// the dynamic-LDS allowance of an RB build of a sweep kernel: once per sampler, kernel and size
+template <class K>
+void rb_allow_lds(dwx_sampler *s, K kernel, size_t lds) {
+  const std::pair<const void *, size_t> key(reinterpret_cast<const void *>(kernel), lds);
+  if (s->rb_lds_allowed.insert(key).second) rt::allow_dynamic_lds(kernel, lds);
+}
+
 // launch the sweep kernel (+ the oversized-variable kernel) over tiles [t0, t1) of launch l
 // multi (inference of a graph without degree-binned variables): P.n_sweeps sweeps per launch
 // covered (if given): the end of the gap-free run of weight-sorted super-tiles that starts at t0 (t0: none)
-template <bool LEARN>
+// RB (inference only): the builds that add every draw's conditional to P.rb (dwx_rb_enable)
+template <bool LEARN, bool RB = false>
 uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, uint32_t t1, const bool multi = false,
                       uint32_t *covered = nullptr) {
+  static_assert(!(LEARN && RB), "Rao-Blackwellised sums: inference sweeps only");
   const CompiledGraph &c = *s->cg;
   if (covered) *covered = t0;
   if (t1 <= t0) return 0;
@@ -344,49 +358,56 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
   // (all-unary graphs stage 8-byte terms whenever the compute phase needs no record)
   const size_t lds = tab8 ? s->lds_tab : slim ? s->lds_learn_pull : s->lds_bytes[LEARN ? 1 : 0];
   constexpr int RPC = (int)ROWPTR_UNROLL_CAT;
+  // (the RB builds are set up when they are first launched, not at create: a sampler that never enables pays
+  // nothing.  The persistent grid is the one sized from the plain build's occupancy: a build that keeps fewer
+  // workgroups resident runs the surplus ones after the first leave -- correct, the tiles are strided.)
+  auto go = [&](auto kernel) {
+    if (RB) rb_allow_lds(s, kernel, lds);
+    rt::launch(kernel, grid, BLOCK_THREADS, lds, s->stream, P);
+  };
 
   if constexpr (!LEARN) {
     if (multi) {   // (only asked for on compact-record graphs, never on the terms table)
       constexpr int RP = (int)ROWPTR_UNROLL;
-      if (s->rp_cat) rt::launch(sweep8_kernel<false, 6, false, RPC, true>, grid, BLOCK_THREADS, lds, s->stream, P);
+      if (s->rp_cat) go(sweep8_kernel<false, 6, false, RPC, true, RB>);
       else switch (s->stage_k) {
-        case 3: rt::launch(sweep8_kernel<false, 3, false, RP, true>, grid, BLOCK_THREADS, lds, s->stream, P); break;
-        case 6: rt::launch(sweep8_kernel<false, 6, false, RP, true>, grid, BLOCK_THREADS, lds, s->stream, P); break;
-        default: rt::launch(sweep8_kernel<false, 12, false, RP, true>, grid, BLOCK_THREADS, lds, s->stream, P); break;
+        case 3: go(sweep8_kernel<false, 3, false, RP, true, RB>); break;
+        case 6: go(sweep8_kernel<false, 6, false, RP, true, RB>); break;
+        default: go(sweep8_kernel<false, 12, false, RP, true, RB>); break;
       }
       ++launches;
       return;
     }
   }
   if (rec8 && s->rp_cat) {
-    if (tab8) rt::launch(sweep8_kernel<false, 6, true, RPC>, grid, BLOCK_THREADS, lds, s->stream, P);
-    else rt::launch(sweep8_kernel<LEARN, 6, false, RPC>, grid, BLOCK_THREADS, lds, s->stream, P);
+    if (tab8) go(sweep8_kernel<false, 6, true, RPC, false, RB>);
+    else go(sweep8_kernel<LEARN, 6, false, RPC, false, RB>);
   } else if (tab8) {
     switch (s->stage_k) {
-      case 3: rt::launch(sweep8_kernel<false, 3, true>, grid, BLOCK_THREADS, lds, s->stream, P); break;
-      case 6: rt::launch(sweep8_kernel<false, 6, true>, grid, BLOCK_THREADS, lds, s->stream, P); break;
-      default: rt::launch(sweep8_kernel<false, 12, true>, grid, BLOCK_THREADS, lds, s->stream, P); break;
+      case 3: go(sweep8_kernel<false, 3, true, (int)ROWPTR_UNROLL, false, RB>); break;
+      case 6: go(sweep8_kernel<false, 6, true, (int)ROWPTR_UNROLL, false, RB>); break;
+      default: go(sweep8_kernel<false, 12, true, (int)ROWPTR_UNROLL, false, RB>); break;
     }
   } else if (rec8) {
     switch (s->stage_k) {
-      case 3: rt::launch(sweep8_kernel<LEARN, 3>, grid, BLOCK_THREADS, lds, s->stream, P); break;
-      case 6: rt::launch(sweep8_kernel<LEARN, 6>, grid, BLOCK_THREADS, lds, s->stream, P); break;
-      default: rt::launch(sweep8_kernel<LEARN, 12>, grid, BLOCK_THREADS, lds, s->stream, P); break;
+      case 3: go(sweep8_kernel<LEARN, 3, false, (int)ROWPTR_UNROLL, false, RB>); break;
+      case 6: go(sweep8_kernel<LEARN, 6, false, (int)ROWPTR_UNROLL, false, RB>); break;
+      default: go(sweep8_kernel<LEARN, 12, false, (int)ROWPTR_UNROLL, false, RB>); break;
     }
   } else if (s->tv_pair) {
     // every tile pre-signed unary and / or inline arity-2 records (config 3b / 5b): the small build
-    rt::launch(sweep_kernel<LEARN, 6, LEARN, TV_PAIR>, grid, BLOCK_THREADS, lds, s->stream, P);
+    go(sweep_kernel<LEARN, 6, LEARN, TV_PAIR, RB>);
   } else if (LEARN && s->wide_learn) {
     switch (s->stage_k) {
-      case 3: rt::launch(sweep_kernel<LEARN, 3, LEARN>, grid, BLOCK_THREADS, lds, s->stream, P); break;
-      case 6: rt::launch(sweep_kernel<LEARN, 6, LEARN>, grid, BLOCK_THREADS, lds, s->stream, P); break;
-      default: rt::launch(sweep_kernel<LEARN, 12, LEARN>, grid, BLOCK_THREADS, lds, s->stream, P); break;
+      case 3: go(sweep_kernel<LEARN, 3, LEARN, TV_ALL, RB>); break;
+      case 6: go(sweep_kernel<LEARN, 6, LEARN, TV_ALL, RB>); break;
+      default: go(sweep_kernel<LEARN, 12, LEARN, TV_ALL, RB>); break;
     }
   } else {
     switch (s->stage_k) {
-      case 3: rt::launch(sweep_kernel<LEARN, 3>, grid, BLOCK_THREADS, lds, s->stream, P); break;
-      case 6: rt::launch(sweep_kernel<LEARN, 6>, grid, BLOCK_THREADS, lds, s->stream, P); break;
-      default: rt::launch(sweep_kernel<LEARN, 12>, grid, BLOCK_THREADS, lds, s->stream, P); break;
+      case 3: go(sweep_kernel<LEARN, 3, false, TV_ALL, RB>); break;
+      case 6: go(sweep_kernel<LEARN, 6, false, TV_ALL, RB>); break;
+      default: go(sweep_kernel<LEARN, 12, false, TV_ALL, RB>); break;
     }
   }
   ++launches;
@@ -441,14 +462,17 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
             P.super_rot = n_cached;   // (cached ones lead the run: the range is the launch's first tiles)
         }
         // (one distinct d: the UNI build keeps it in a scalar register; DWX_NO_SORT_UNI: A/B knob)
-        if (s->n_sort_dvals == 2 && !s->no_sort_uni)
-          rt::launch(sorted_sweep_kernel<LEARN, true>, (unsigned)(r.b - r.a), SORT_THREADS, s->lds_sorted, s->stream, P,
+        if (s->n_sort_dvals == 2 && !s->no_sort_uni) {
+          if (RB) rb_allow_lds(s, sorted_sweep_kernel<LEARN, true, RB>, s->lds_sorted);
+          rt::launch(sorted_sweep_kernel<LEARN, true, RB>, (unsigned)(r.b - r.a), SORT_THREADS, s->lds_sorted, s->stream, P,
                      (const SuperTile *)(d_sv + r.a), (uint32_t)(r.b - r.a), d_sr,
                      (const double *)s->d_sort_dvals, s->n_sort_dvals);
-        else
-          rt::launch(sorted_sweep_kernel<LEARN, false>, (unsigned)(r.b - r.a), SORT_THREADS, s->lds_sorted, s->stream, P,
+        } else {
+          if (RB) rb_allow_lds(s, sorted_sweep_kernel<LEARN, false, RB>, s->lds_sorted);
+          rt::launch(sorted_sweep_kernel<LEARN, false, RB>, (unsigned)(r.b - r.a), SORT_THREADS, s->lds_sorted, s->stream, P,
                      (const SuperTile *)(d_sv + r.a), (uint32_t)(r.b - r.a), d_sr,
                      (const double *)s->d_sort_dvals, s->n_sort_dvals);
+        }
         ++launches;
         P.super_rot = 0;
         cursor = sv[r.b - 1].tile0 + sv[r.b - 1].ntiles;
@@ -461,7 +485,7 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
   P.tile_end = t1;
   // categorical oversized variables: a workgroup each
   if (cg1 > cg0) {
-    rt::launch(giant_kernel<LEARN>, cg1 - cg0, GIANT_THREADS, 0, st_giant, P,
+    rt::launch(giant_kernel<LEARN, RB>, cg1 - cg0, GIANT_THREADS, 0, st_giant, P,
                (const uint32_t *)(s->d_giant + cg0), cg1 - cg0);
     ++launches;
   }
@@ -470,7 +494,7 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
     const uint32_t p0 = s->bgiant_piece_off[bg0], np = s->bgiant_piece_off[bg1] - p0;
     rt::launch(giant_pot_kernel<LEARN>, np, GIANT_THREADS, 0, st_giant, P, (const uint32_t *)s->d_bgiant,
                (const GiantPiece *)s->d_bgiant_pieces, p0, np, s->d_bgiant_partial);
-    rt::launch(giant_decide_kernel<LEARN>, (bg1 - bg0 + BLOCK_THREADS - 1) / BLOCK_THREADS, BLOCK_THREADS, 0, st_giant, P,
+    rt::launch(giant_decide_kernel<LEARN, RB>, (bg1 - bg0 + BLOCK_THREADS - 1) / BLOCK_THREADS, BLOCK_THREADS, 0, st_giant, P,
                (const uint32_t *)s->d_bgiant, (const uint32_t *)s->d_bgiant_piece_off, bg0, bg1 - bg0,
                (const double *)s->d_bgiant_partial, s->d_bgiant_decision);
     launches += 2;
@@ -483,7 +507,7 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
   // mid-degree variables among these tiles: a wave each
   if (w1 > w0) {
     const uint32_t per_block = BLOCK_THREADS / 64u;
-    rt::launch(wide_kernel<LEARN>, (w1 - w0 + per_block - 1) / per_block, BLOCK_THREADS, 0, st_wide, P,
+    rt::launch(wide_kernel<LEARN, RB>, (w1 - w0 + per_block - 1) / per_block, BLOCK_THREADS, 0, st_wide, P,
                (const uint32_t *)(s->d_wide + w0), w1 - w0);
     ++launches;
   }
@@ -513,6 +537,7 @@ void enqueue_inference_multi(dwx_sampler *s, uint32_t n) {
   P.sweep = s->sweep;
   P.n_sweeps = n;
   P.edge_terms = nullptr;
+  P.rb = s->rb_on ? s->d_rb : nullptr;
   TimedSpan sp{};
   if (s->timing) {
     sp.a = rt::event_create(); sp.b = rt::event_create(); sp.c = rt::event_create(); sp.kind = 0;
@@ -521,7 +546,8 @@ void enqueue_inference_multi(dwx_sampler *s, uint32_t n) {
   uint32_t launches = 0;
   for (size_t l = 0; l + 1 < c.launch_off.size(); ++l) {
     const uint32_t t1 = s->opts.sample_evidence ? c.launch_tile[l + 1] : c.launch_query_tile_end[l];
-    launches += launch_tiles<false>(s, P, l, c.launch_tile[l], t1, true);
+    launches += P.rb ? launch_tiles<false, true>(s, P, l, c.launch_tile[l], t1, true)
+                     : launch_tiles<false>(s, P, l, c.launch_tile[l], t1, true);
   }
   if (s->timing) {
     rt::event_record(sp.b, s->stream);
@@ -560,6 +586,7 @@ void enqueue_inference(dwx_sampler *s) {
   rt::set_device(s->device);
   KernelParams P = s->base;
   P.sweep = s->sweep;
+  P.rb = s->rb_on ? s->d_rb : nullptr;
   s->last_infer = true;
   // The second consecutive inference sweep on the same weights tabulates the pre-signed
   // records' potential terms (one extra pass, about the cost of a sweep); from then on
@@ -593,7 +620,8 @@ void enqueue_inference(dwx_sampler *s) {
     // only the query variables' tiles unless --sample_evidence (src/gibbs_sampler.h:157)
     const uint32_t t1 = s->opts.sample_evidence ? c.launch_tile[l + 1] : c.launch_query_tile_end[l];
     uint32_t covered = 0;
-    launches += launch_tiles<false>(s, P, l, c.launch_tile[l], t1, false, &covered);
+    launches += P.rb ? launch_tiles<false, true>(s, P, l, c.launch_tile[l], t1, false, &covered)
+                     : launch_tiles<false>(s, P, l, c.launch_tile[l], t1, false, &covered);
     // valid for launch l only if sorted_sweep_kernel stored the sum of EVERY query tile (none took the
     // tile sweep, the terms table or a degree-bin kernel)
     if (P.pot && c.launch_query_tile_end[l] > c.launch_tile[l] && covered >= c.launch_query_tile_end[l]) s->pot_valid[l] = 1;
@@ -2457,8 +2485,53 @@ int dwx_clear_tallies(dwx_sampler *s) {
   return guarded([&]() {
     rt::set_device(s->device);
     rt::dmemset(s->d_tally, 0, s->cg->R * 4, s->stream);
+    if (s->d_rb) rt::dmemset(s->d_rb, 0, s->cg->R * 8, s->stream);
     s->infer_sweeps = 0;
   });
+}
+
+int dwx_rb_enable(dwx_sampler *s, int on) {
+  if (!s) return fail(DWX_E_INVALID, "null sampler");
+  if (!on) { s->rb_on = false; return DWX_OK; }
+  if (!s->d_rb) {
+    int rc = guarded([&]() {
+      rt::set_device(s->device);
+      const size_t bytes = ((size_t)s->cg->R + 1) * 8;
+#ifdef DWX_EMU
+      void *p = rt::dmalloc(bytes);
+#else
+      void *p = rt::try_dmalloc(bytes);
+#endif
+      if (!p) return;
+      rt::dmemset(p, 0, bytes, s->stream);
+      s->d_rb = (unsigned long long *)p;
+    });
+    if (rc != DWX_OK) return rc;
+    if (!s->d_rb) return fail(DWX_E_NOMEM, "no device memory for the Rao-Blackwellised sums (8 bytes per value row)");
+  }
+  s->rb_on = true;
+  return DWX_OK;
+}
+
+int dwx_get_rb_sums(dwx_sampler *s, uint64_t *sums, uint64_t *nsamples) {
+  if (!s) return fail(DWX_E_INVALID, "null sampler");
+  if (!s->d_rb) return fail(DWX_E_INVALID, "Rao-Blackwellised sums were never enabled (dwx_rb_enable)");
+  int rc = DWX_OK;
+  if (sums) rc = guarded([&]() {
+    const CompiledGraph &c = *s->cg;
+    rt::set_device(s->device);
+    RawArray<unsigned long long> t(c.R);
+    rt::d2h(t.data(), s->d_rb, c.R * 8, s->stream);
+    rt::stream_sync(s->stream);
+    parallel_ranges(c.Vo, host_threads(), [&](uint64_t pb, uint64_t pe) {
+      for (uint64_t p = pb; p < pe; ++p) {
+        const uint64_t rb = c.ref_var_val_base[c.perm[p]];
+        for (uint32_t r = c.v_row[p]; r < c.v_row[p + 1]; ++r) sums[rb + (r - c.v_row[p])] = t[r];
+      }
+    });
+  });
+  if (rc != DWX_OK) return rc;
+  return nsamples ? dwx_get_tallies(s, nullptr, nsamples) : DWX_OK;
 }
 
 int dwx_get_tallies(dwx_sampler *s, uint64_t *tallies, uint64_t *nsamples) {
@@ -2530,6 +2603,7 @@ int dwx_device_buffer(dwx_sampler *s, int which, void **dev_ptr, uint64_t *nbyte
     case DWX_BUF_ASSIGN_FREE: *dev_ptr = s->d_assign_free; *nbytes = c.V * 4; break;
     case DWX_BUF_ASSIGN_EVID: *dev_ptr = s->d_assign_evid; *nbytes = c.V * 4; break;
     case DWX_BUF_TALLIES: *dev_ptr = s->d_tally; *nbytes = c.R * 4; break;
+    case DWX_BUF_RB: *dev_ptr = s->d_rb; *nbytes = s->d_rb ? c.R * 8 : 0; break;
     case DWX_BUF_TSTATIC: {
       auto it = s->levels.find(1);
       *dev_ptr = it == s->levels.end() ? nullptr : it->second->d_t_static;

@@ -230,7 +230,9 @@ DWX_DEV void store_learn_rec(LearnRec16 *dst, const EdgeRec &r, float w, bool pr
   lr.b = presigned ? miss : bits_to_float(cu1 | cu0 << 2 | ce1 << 4 | ce0 << 6);
   *dst = lr;
 }
-template <bool LEARN, int K, bool WIDE = false, uint32_t TV = TV_ALL>
+// RB (inference builds): every draw's conditional is added to P.rb (tile_walk.h, rb_*); the host launches these
+// builds only while dwx_rb_enable is on, the default builds contain none of it.
+template <bool LEARN, int K, bool WIDE = false, uint32_t TV = TV_ALL, bool RB = false>
 // (the learning kernel's LDS footprint admits 2 workgroups per CU at K = 12: give the
 // register allocator the matching budget instead of spilling at the 3-per-CU limit)
 // (the TV_PAIR learning build stages 16-byte records: its LDS footprint admits DWX_PAIR_WG workgroups per CU)
@@ -499,9 +501,9 @@ __global__ void __launch_bounds__(BLOCK_THREADS, WIDE ? (K <= 6 ? ((TV & TV_TERM
       else if ((TV & TV_SIMPLE) && LEARN && pull)   // the staged records ARE terms: sgd_row is never reached (want_delta)
         delta = process_variable<LEARN, W_TERMS, true, false, NOCAT>(P, T, d.v0 + t, pre, A, B, true);
       else if (((TV & TV_SIMPLE) && (d.flags & TILE_SIMPLE)) || ((TV & TV_T23) && K <= 6 && !LEARN && (d.flags & (TILE_TERMS2 | TILE_TERMS3))))
-        delta = process_variable<LEARN, LEARN ? W_ARRAY : W_TERMS, true, false, NOCAT>(P, T, d.v0 + t, pre, A, B, false);
+        delta = process_variable<LEARN, LEARN ? W_ARRAY : W_TERMS, true, false, NOCAT, RB>(P, T, d.v0 + t, pre, A, B, false);
       else if (TV & TV_GENERIC)
-        process_variable<LEARN, WMODE, false>(P, T, d.v0 + t, pre, A, B);
+        process_variable<LEARN, WMODE, false, false, false, RB>(P, T, d.v0 + t, pre, A, B);
     }
     if (pull || pull_unary) {
       // every wave of the tile publishes its two ballots (also when all zero: the words
@@ -570,11 +572,12 @@ __global__ void __launch_bounds__(BLOCK_THREADS, WIDE ? (K <= 6 ? ((TV & TV_TERM
 // kernel's weight update: its own loads then return under the record stream's instead of before it).
 struct NoPrologue { DWX_DEV void operator()() const {} };
 template <bool LEARN, int K, bool TAB = false, int RP = (int)ROWPTR_UNROLL, bool MULTI = false, bool LW = false,
-          bool ONE = false, class Pre = NoPrologue>
+          bool ONE = false, bool RB = false, class Pre = NoPrologue>
 DWX_DEV void sweep8_body(const KernelParams &P, const float *lw32, Pre pre_fn = Pre()) {
   static_assert(!(LEARN && TAB), "the terms table serves inference sweeps only");
   static_assert(!MULTI || (!LEARN && !TAB), "several sweeps per launch: the gathering inference build");
   static_assert(!LW || (LEARN && !TAB && !MULTI), "LDS weights: the learning build");
+  static_assert(!RB || !LEARN, "Rao-Blackwellised sums: inference builds");
   DWX_DYN_LDS(dyn_lds);
   uint32_t *s_rowptr = (uint32_t *)dyn_lds;
   double *s_pot = (double *)(dyn_lds + P.lds_pot_off);
@@ -687,12 +690,12 @@ DWX_DEV void sweep8_body(const KernelParams &P, const float *lw32, Pre pre_fn = 
         const uint32_t n = P.n_sweeps;
         const uint32_t S = (n >= MULTI_SLICE_MIN_SWEEPS && d.nv < BLOCK_THREADS) ? MULTI_SLICES : 1u;   // uniform
         if (S == 1u) {   // (its own call: the loop over the sweeps keeps scalar bounds)
-          if (t < d.nv) infer_variable_multi<W_TERMS, true>(P, T, d.v0 + t, pre, 0u, n, true);
+          if (t < d.nv) infer_variable_multi<W_TERMS, true, RB>(P, T, d.v0 + t, pre, 0u, n, true);
         } else for (uint32_t item = t; item < S * d.nv; item += BLOCK_THREADS) {
           const uint32_t sl = item / d.nv, var = item - sl * d.nv;
           const VarPre vp = var == t ? pre : load_var_pre<false, false>(P, d.v0 + var);
           const uint32_t k_lo = (uint32_t)((uint64_t)n * sl / S), k_hi = (uint32_t)((uint64_t)n * (sl + 1) / S);
-          infer_variable_multi<W_TERMS, true>(P, T, d.v0 + var, vp, k_lo, k_hi, sl + 1 == S);
+          infer_variable_multi<W_TERMS, true, RB>(P, T, d.v0 + var, vp, k_lo, k_hi, sl + 1 == S);
         }
       }
     } else if (fits && t < d.nv) {
@@ -700,7 +703,7 @@ DWX_DEV void sweep8_body(const KernelParams &P, const float *lw32, Pre pre_fn = 
       if (LEARN && pull)   // the staged records ARE terms: sgd_row is never reached (want_delta)
         delta = process_variable<LEARN, W_TERMS8, true, true>(P, T, d.v0 + t, pre, A, B, true);
       else   // (FIXED: boolean variables of a compact-record graph sum their potentials in fixed point)
-        process_variable<LEARN, LEARN ? W_ARRAY : (TAB ? W_TERMS8 : W_TERMS), true, true>(P, T, d.v0 + t, pre, A, B, false);
+        process_variable<LEARN, LEARN ? W_ARRAY : (TAB ? W_TERMS8 : W_TERMS), true, true, false, RB>(P, T, d.v0 + t, pre, A, B, false);
     }
     if (pull) {
       const unsigned long long nz = DWX_BALLOT(delta != 0), ng = DWX_BALLOT(delta < 0);
@@ -717,9 +720,9 @@ DWX_DEV void sweep8_body(const KernelParams &P, const float *lw32, Pre pre_fn = 
   }
   flush_accumulators(P, s_agg, t);
 }
-template <bool LEARN, int K, bool TAB = false, int RP = (int)ROWPTR_UNROLL, bool MULTI = false>
+template <bool LEARN, int K, bool TAB = false, int RP = (int)ROWPTR_UNROLL, bool MULTI = false, bool RB = false>
 __global__ void __launch_bounds__(BLOCK_THREADS, TAB ? 4 : (LEARN ? DWX_S8_LEARN_WG : DWX_S8_INFER_WG)) sweep8_kernel(const KernelParams P) {
-  sweep8_body<LEARN, K, TAB, RP, MULTI, false>(P, nullptr);
+  sweep8_body<LEARN, K, TAB, RP, MULTI, false, false, RB>(P, nullptr);
 }
 
 // ---------------------------------------------------------------- weight-sorted super-tiles
@@ -747,7 +750,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS, TAB ? 4 : (LEARN ? DWX_S8_LEARN
 // UNI: the table of distinct d holds ONE value besides entry 0 (every record the same function and
 // feature value -- config 3: d = 2): it rides in a scalar register, the per-record ds_read_b64 of the
 // table goes away (round 4; the index is still what tells a zero-filled lane past the end: di == 0).
-template <bool LEARN, bool UNI = false>
+template <bool LEARN, bool UNI = false, bool RB = false>
 __global__ void __launch_bounds__(SORT_THREADS, SORT_WG_PER_CU)
 sorted_sweep_kernel(const KernelParams P, const SuperTile *supers, uint32_t n_supers, const SortRec8 *recs,
                     const double *dvals, uint32_t n_dvals) {
@@ -826,7 +829,7 @@ sorted_sweep_kernel(const KernelParams P, const SuperTile *supers, uint32_t n_su
       const double x = pot_unfix(sum);
       TileView T{nullptr, 0u, nullptr, 0u, nullptr, nullptr, nullptr};
       T.presum = &x;
-      delta = process_variable<LEARN, W_FIXSUM, true>(P, T, ps.p, ps.pre, A, B, true);
+      delta = process_variable<LEARN, W_FIXSUM, true, false, false, RB>(P, T, ps.p, ps.pre, A, B, true);
     }
     if (LEARN) {
       const unsigned long long nz = DWX_BALLOT(delta != 0), ng = DWX_BALLOT(delta < 0);
@@ -847,7 +850,7 @@ sorted_sweep_kernel(const KernelParams P, const SuperTile *supers, uint32_t n_su
 // tallies once, the gradient rows shared out.  (The partial sums re-associate the f64
 // additions: a potential can differ from the sequential sum in its last bits; a decision flips
 // only if r*(1+e^x) is within ~1e-16 of 1.)
-template <bool LEARN>
+template <bool LEARN, bool RB = false>
 __global__ void __launch_bounds__(GIANT_THREADS) giant_kernel(const KernelParams P, const uint32_t *giant_tiles,
                                                               uint32_t n) {
   if (blockIdx.x >= n) return;
@@ -857,7 +860,7 @@ __global__ void __launch_bounds__(GIANT_THREADS) giant_kernel(const KernelParams
   double A, B;
   philox_uniforms(P.seed, P.vid_offset + vp.orig, P.sweep, A, B);
   const TileView T{P.row_ptr, 0u, P.edges, 0u, nullptr, nullptr, nullptr};
-  process_variable<LEARN, W_COOPB, false>(P, T, p, vp, A, B);
+  process_variable<LEARN, W_COOPB, false, false, false, RB>(P, T, p, vp, A, B);
 }
 
 // BOOLEAN oversized variables, several workgroups each.  One workgroup sits on one CU, and a CU
@@ -910,7 +913,7 @@ giant_pot_kernel(const KernelParams P, const uint32_t *bgiant_tiles, const Giant
   }
 }
 
-template <bool LEARN>
+template <bool LEARN, bool RB = false>
 __global__ void __launch_bounds__(BLOCK_THREADS)
 giant_decide_kernel(const KernelParams P, const uint32_t *bgiant_tiles, const uint32_t *piece_off, uint32_t slot0,
                     uint32_t n, const double *partial, uint32_t *decision) {
@@ -928,7 +931,7 @@ giant_decide_kernel(const KernelParams P, const uint32_t *bgiant_tiles, const ui
   philox_uniforms(P.seed, P.vid_offset + vp.orig, P.sweep, A, B);
   TileView T{P.row_ptr, 0u, P.edges, 0u, nullptr, nullptr, nullptr};
   T.presum = sums; T.decision = dec;
-  process_variable<LEARN, W_PRESUM, false>(P, T, p, vp, A, B);
+  process_variable<LEARN, W_PRESUM, false, false, false, RB>(P, T, p, vp, A, B);
 }
 
 __global__ void __launch_bounds__(GIANT_THREADS)
@@ -954,7 +957,7 @@ giant_grad_kernel(const KernelParams P, const uint32_t *bgiant_tiles, const Gian
 // truthiness -- with W_COOP doing stores and tallies once and sharing the gradient rows out.
 // As in giant_kernel the potential is a re-associated f64 sum: it can differ from the
 // sequential one in its last bits; a draw flips only within ~1e-16 of its threshold.
-template <bool LEARN>
+template <bool LEARN, bool RB = false>
 __global__ void __launch_bounds__(BLOCK_THREADS) wide_kernel(const KernelParams P, const uint32_t *wide_tiles,
                                                              uint32_t n) {
   const uint32_t idx = blockIdx.x * (BLOCK_THREADS / 64u) + (threadIdx.x >> 6);
@@ -965,7 +968,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) wide_kernel(const KernelParams 
   double A, B;
   philox_uniforms(P.seed, P.vid_offset + vp.orig, P.sweep, A, B);
   const TileView T{P.row_ptr, 0u, P.edges, 0u, nullptr, nullptr, nullptr};
-  process_variable<LEARN, W_COOP, false>(P, T, p, vp, A, B);
+  process_variable<LEARN, W_COOP, false, false, false, RB>(P, T, p, vp, A, B);
 }
 
 }  // namespace dwx

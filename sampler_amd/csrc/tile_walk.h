@@ -571,6 +571,41 @@ DWX_DEV void bool_potentials_both(const KernelParams &P, const TileView &T, uint
   }
 }
 
+// ---------------------------------------------------------------- Rao-Blackwellised marginals
+// KernelParams::rb (DWX_BUF_RB, uint64 per value row, null = off): instead of counting the value an inference
+// draw picked, add the exact conditional P(x_v = d | everything else) the draw was made from -- the "mixture"
+// estimator of Gelfand & Smith (1990); same chain, same expectation, smaller variance.  The reference has no
+// counterpart (it only counts: src/gibbs_sampler.h:160-167).  The conditional is summed in unsigned 32.32 fixed
+// point so that the sums do not depend on kernel choice, launch geometry or rank count (DESIGN.md 4, items 3
+// and 7); every expression below is evaluated HERE and nowhere else, in f64 with the f64 exp -- the draws' f32
+// tiers are biased in one direction by up to 1e-5 and an average does not remove a bias.
+// Every value row has one owner per sweep and sweeps are stream-ordered: the no-return 64-bit atomic is a
+// fire-and-forget add like the tallies', not a contended one.
+constexpr double RB_SCALE = 4294967296.0;   // 2^32
+// boolean: P(x = 1) = 1 / (1 + exp(pn - pp))  (src/gibbs_sampler.h:204-214 accepts 1 with this probability)
+DWX_DEV unsigned long long rb_bool_q(double pp, double pn) {
+  return (unsigned long long)llrint(RB_SCALE / (1.0 + exp(pn - pp)));
+}
+// categorical: e_d = exp(pot_d - m), m = max_j pot_j; S = e_0 + e_1 + ... in value order; P(x = d) = e_d / S
+DWX_DEV double rb_cat_e(double pot, double m) { return exp(pot - m); }
+DWX_DEV unsigned long long rb_cat_q(double e, double S) {
+  return (unsigned long long)llrint(RB_SCALE * e / S);
+}
+DWX_DEV void rb_add(const KernelParams &P, uint32_t row, unsigned long long q) {
+  atomicAdd(&P.rb[row], q);
+}
+// The add of a boolean variable's single-sweep draw (process_variable): its lane is the row's only writer in the
+// launch, so a load-add-store would be correct THERE -- and only there: the sliced multi-sweep path
+// (infer_variable_multi, MULTI_SLICES) has several lanes adding to one row in one launch and needs the atomic.
+// DWX_EXP_RB_LAS builds that form for the A/B of profiles/r05/rao_blackwell.md; the product keeps the atomic.
+DWX_DEV void rb_add_owner(const KernelParams &P, uint32_t row, unsigned long long q) {
+#ifdef DWX_EXP_RB_LAS
+  P.rb[row] = P.rb[row] + q;
+#else
+  atomicAdd(&P.rb[row], q);
+#endif
+}
+
 #ifndef DWX_DRAW_GUARD
 #define DWX_DRAW_GUARD 1e-4
 #endif
@@ -578,6 +613,27 @@ DWX_DEV void bool_potentials_both(const KernelParams &P, const TileView &T, uint
 // categorical draw of a small domain goes through the second, linear-space tier -- parity over it)
 constexpr double DRAW_GUARD = DWX_DRAW_GUARD;   // >> every f32 error bound below
 constexpr uint32_t SMALL_CARD = 8;    // domains up to this size are drawn out of registers
+
+// a small domain's potentials out of registers (pot[d] for d < card, m their maximum): `times` sweeps' worth
+DWX_DEV void rb_cat_small(const KernelParams &P, uint32_t row0, uint32_t card, const double (&pot)[SMALL_CARD],
+                          double m, unsigned long long times) {
+  double e[SMALL_CARD];
+  double S = 0.0;
+#pragma unroll
+  for (uint32_t d = 0; d < SMALL_CARD; ++d) {
+    e[d] = d < card ? rb_cat_e(pot[d], m) : 0.0;
+    if (d < card) S += e[d];
+  }
+#pragma unroll
+  for (uint32_t d = 0; d < SMALL_CARD; ++d)
+    if (d < card) rb_add(P, row0 + d, times * rb_cat_q(e[d], S));
+}
+// ... out of memory (the tile's LDS scratch): pot[0, card)
+DWX_DEV void rb_cat_rows(const KernelParams &P, uint32_t row0, uint32_t card, const double *pot, double m) {
+  double S = 0.0;
+  for (uint32_t d = 0; d < card; ++d) S += rb_cat_e(pot[d], m);
+  for (uint32_t d = 0; d < card; ++d) rb_add(P, row0 + d, rb_cat_q(rb_cat_e(pot[d], m), S));
+}
 
 // src/gibbs_sampler.h:204-214: proposal 1 iff r * (1 + exp(pn - pp)) < 1.
 // Fast path: the same quantity with an f32 exp (relative error < 1e-5 for |x| < 30); its
@@ -600,7 +656,9 @@ DWX_DEV uint32_t bool_draw(double r, double pp, double pn) {
 // the first d whose cumulative mass reaches r; accepted only if r is at least DRAW_GUARD
 // away from both cumulative boundaries of that d (f32 error of a boundary < 1e-5, the
 // reference's own logadd cut-off shifts it by < 1e-8); otherwise the exact sequence runs.
-template <int WMODE, bool SIMPLE>
+// RB (inference draws only): the conditional these potentials define goes to P.rb (rb_cat_*) -- once per
+// call, by the group's leader lane in a cooperative walk.
+template <int WMODE, bool SIMPLE, bool RB = false>
 DWX_DEV uint32_t cat_draw(const KernelParams &P, const TileView &T, uint32_t row0, uint32_t card,
                           const uint32_t *assign, uint32_t me, double r) {
   if (SIMPLE && card <= SMALL_CARD) {
@@ -621,6 +679,7 @@ DWX_DEV uint32_t cat_draw(const KernelParams &P, const TileView &T, uint32_t row
         m = pot[d] > m ? pot[d] : m;
       }
     }
+    if (RB) rb_cat_small(P, row0, card, pot, m, 1ull);
     float ex[SMALL_CARD];
     float S = 0.f;
 #pragma unroll
@@ -714,6 +773,7 @@ DWX_DEV uint32_t cat_draw(const KernelParams &P, const TileView &T, uint32_t row
       pot[d] = v;
       m = v > m ? v : m;
     }
+    if (RB) rb_cat_rows(P, row0, card, pot, m);
     float S = 0.f;
     for (uint32_t d = 0; d < card; ++d) {
       const double z = pot[d] - m;
@@ -740,6 +800,18 @@ DWX_DEV uint32_t cat_draw(const KernelParams &P, const TileView &T, uint32_t row
     return card - 1;  // the reference asserts here (:243); rounding can leave r > 0
   }
   // no scratch (oversized variable): recompute potentials instead of buffering them
+  if (RB) {   // (three more walks over the rows: maximum, normaliser, terms -- same order as rb_cat_rows)
+    double m = -1e300, S = 0.0;
+    for (uint32_t d = 0; d < card; ++d) {
+      const double v = row_potential<WMODE, SIMPLE>(P, T, row0 + d, assign, me, d);
+      m = v > m ? v : m;
+    }
+    for (uint32_t d = 0; d < card; ++d) S += rb_cat_e(row_potential<WMODE, SIMPLE>(P, T, row0 + d, assign, me, d), m);
+    for (uint32_t d = 0; d < card; ++d) {
+      const double e = rb_cat_e(row_potential<WMODE, SIMPLE>(P, T, row0 + d, assign, me, d), m);
+      if (!Coop<WMODE>::on || Coop<WMODE>::lane() == 0u) rb_add(P, row0 + d, rb_cat_q(e, S));
+    }
+  }
   double sum = -100000.0;
   for (uint32_t d = 0; d < card; ++d)
     sum = logadd(sum, row_potential<WMODE, SIMPLE>(P, T, row0 + d, assign, me, d));
@@ -878,7 +950,8 @@ DWX_DEV VarPre load_var_pre(const KernelParams &P, uint32_t p) {
 // [k_lo, k_hi): the slice of the launch's sweeps this call draws (a tile with fewer variables
 // than lanes cuts a long run of sweeps into slices, so that every lane draws: sweep8_kernel);
 // the slice that holds the last sweep stores the assignment.
-template <int WMODE, bool FIXED>
+// RB: a sweep-invariant conditional is added (k_hi - k_lo) times in one add per value row.
+template <int WMODE, bool FIXED, bool RB = false>
 DWX_DEV void infer_variable_multi(const KernelParams &P, const TileView &T, uint32_t p, const VarPre pre,
                                   const uint32_t k_lo, const uint32_t k_hi, const bool store) {
   const uint32_t meta = pre.meta;
@@ -898,6 +971,7 @@ DWX_DEV void infer_variable_multi(const KernelParams &P, const TileView &T, uint
       count += prop;
     }
     if (count) atomicAdd(&P.tally[row0], count);
+    if (RB && k_hi > k_lo) rb_add(P, row0, (unsigned long long)(k_hi - k_lo) * rb_bool_q(pp, pn));
   } else if (card <= SMALL_CARD) {
     double e[SMALL_CARD];
     uint32_t es = T.rowptr[row0 - T.row_bias];
@@ -909,6 +983,12 @@ DWX_DEV void infer_variable_multi(const KernelParams &P, const TileView &T, uint
         e[d] = range_potential<WMODE, true>(P, T, es, ee, P.assign_evid, p, d);
         es = ee;
       }
+    }
+    if (RB && k_hi > k_lo) {
+      double m = -1e300;
+#pragma unroll
+      for (uint32_t d = 0; d < SMALL_CARD; ++d) if (d < card) m = e[d] > m ? e[d] : m;
+      rb_cat_small(P, row0, card, e, m, (unsigned long long)(k_hi - k_lo));
     }
     double sum = -100000.0;
 #pragma unroll
@@ -954,7 +1034,7 @@ DWX_DEV void infer_variable_multi(const KernelParams &P, const TileView &T, uint
     for (uint32_t k = k_lo; k < k_hi; ++k) {
       double A, B;
       philox_uniforms(P.seed, vid, P.sweep + k, A, B);
-      prop = cat_draw<WMODE, true>(P, T, row0, card, P.assign_evid, p, A);
+      prop = cat_draw<WMODE, true, RB>(P, T, row0, card, P.assign_evid, p, A);
       atomicAdd(&P.tally[row0 + prop], 1u);
     }
   }
@@ -965,7 +1045,8 @@ DWX_DEV void infer_variable_multi(const KernelParams &P, const TileView &T, uint
 // return hit(free) - hit(evid) in {-1,0,+1} for a variable that triggers SGD (0 otherwise).
 // NOCAT: the caller's graph has no categorical lane tile (sweep_kernel's TV_PAIR build): every
 // categorical branch -- cat_draw, the noise-aware rows -- compiles out.
-template <bool LEARN, int WMODE, bool SIMPLE, bool FIXED = false, bool NOCAT = false>
+// RB (inference only): the conditional every draw decides on is added to P.rb (rb_bool_q / rb_cat_*).
+template <bool LEARN, int WMODE, bool SIMPLE, bool FIXED = false, bool NOCAT = false, bool RB = false>
 DWX_DEV int process_variable(const KernelParams &P, const TileView &T, uint32_t p,
                              const VarPre pre, double A, double B, const bool want_delta = false) {
   const uint32_t meta = pre.meta;
@@ -976,6 +1057,7 @@ DWX_DEV int process_variable(const KernelParams &P, const TileView &T, uint32_t 
   // W_COOP: all 64 lanes of the wave run this function for the SAME variable; the potentials
   // are wave-wide sums (identical in every lane), so every lane takes the same decisions;
   // stores and tallies happen once, the gradient rows are shared out over the lanes
+  static_assert(!(LEARN && RB), "Rao-Blackwellised sums: inference sweeps only");
   constexpr bool COOP = Coop<WMODE>::on;
   const bool leader = !COOP || Coop<WMODE>::lane() == 0u;
   if (!LEARN) {
@@ -989,8 +1071,9 @@ DWX_DEV int process_variable(const KernelParams &P, const TileView &T, uint32_t 
       // single owner per row: a no-return atomic is a fire-and-forget increment the
       // wave never waits for (a load-add-store would stall on the load)
       if (prop && leader) atomicAdd(&P.tally[row0], 1u);
+      if (RB && leader) rb_add_owner(P, row0, rb_bool_q(pp, pn));
     } else {
-      prop = cat_draw<WMODE, SIMPLE>(P, T, row0, card, P.assign_evid, p, A);
+      prop = cat_draw<WMODE, SIMPLE, RB>(P, T, row0, card, P.assign_evid, p, A);
       if (leader) atomicAdd(&P.tally[row0 + prop], 1u);
     }
     // (a variable of an all-unary tile has no neighbours: nobody re-reads its assignment)

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DWX_LIB") or os.path.join(HERE, "csrc", "libdwx.so")
 
 DWX_OK, DWX_E_INVALID, DWX_E_LIMIT, DWX_E_DEVICE, DWX_E_NOMEM = 0, -1, -2, -3, -4
-BUF_WEIGHTS, BUF_GRAD, BUF_ASSIGN_FREE, BUF_ASSIGN_EVID, BUF_TALLIES, BUF_TSTATIC, BUF_TSTATIC_PLAN, BUF_SORTED_RECORDS, BUF_SORTED_RECORDS_PLAN = range(9)
+BUF_WEIGHTS, BUF_GRAD, BUF_ASSIGN_FREE, BUF_ASSIGN_EVID, BUF_TALLIES, BUF_TSTATIC, BUF_TSTATIC_PLAN, BUF_SORTED_RECORDS, BUF_SORTED_RECORDS_PLAN, BUF_RB = range(10)
 
 # every symbol include/dwx.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -28,7 +28,7 @@ SYMBOLS = [
     "dwx_wait", "dwx_sgd_plan", "dwx_sgd_curvature", "dwx_sgd_plan_rows", "dwx_sgd_plan_force_dynamic", "dwx_sgd_get_chunks", "dwx_grad_pack32_async", "dwx_grad_unpack32_async", "dwx_grad_pack_async", "dwx_grad_unpack_async", "dwx_sgd_accumulate_async",
     "dwx_sgd_apply_async", "dwx_sgd_finish",
     "dwx_get_weights", "dwx_set_weights", "dwx_average_weights_async",
-    "dwx_clear_tallies", "dwx_get_tallies",
+    "dwx_clear_tallies", "dwx_get_tallies", "dwx_rb_enable", "dwx_get_rb_sums",
     "dwx_get_assignments", "dwx_set_assignments", "dwx_get_sweep", "dwx_set_sweep",
     "dwx_device_buffer", "dwx_halo_create", "dwx_halo_destroy", "dwx_halo_buffer", "dwx_halo_message_bytes", "dwx_halo_pack_async",
     "dwx_halo_unpack_async", "dwx_stream", "dwx_kernel_time", "dwx_kernel_time_reset",
@@ -118,6 +118,8 @@ class Library:
         L.dwx_average_weights_async.argtypes = [vp, C.c_uint32]
         L.dwx_clear_tallies.argtypes = [vp]
         L.dwx_get_tallies.argtypes = [vp, vp, vp]
+        L.dwx_rb_enable.argtypes = [vp, i32]
+        L.dwx_get_rb_sums.argtypes = [vp, vp, vp]
         L.dwx_get_assignments.argtypes = [vp, i32, vp]
         L.dwx_set_assignments.argtypes = [vp, i32, vp]
         L.dwx_get_sweep.argtypes = [vp, vp]; L.dwx_set_sweep.argtypes = [vp, u64]
@@ -338,6 +340,30 @@ class GibbsSampler:
         self.lib.check(self.lib.L.dwx_get_tallies(self.h, t.ctypes.data, n.ctypes.data))
         return t, n
 
+    # ---- Rao-Blackwellised marginals (no reference counterpart; include/dwx.h) ----
+    def rb_enable(self, on=True):
+        """Inference sweeps add the conditional every draw decides on to a 32.32 fixed-point sum per value row."""
+        self.lib.check(self.lib.L.dwx_rb_enable(self.h, int(bool(on))))
+
+    def rb_sums(self):
+        """-> (uint64[num_values] sums of 2^32 * P(x_v = d | rest), uint64[V] nsamples), reference numbering."""
+        t = np.zeros(self.num_values, np.uint64)
+        n = np.zeros(self.V, np.uint64)
+        self.lib.check(self.lib.L.dwx_get_rb_sums(self.h, t.ctypes.data, n.ctypes.data))
+        return t, n
+
+    def rb_marginals(self):
+        """float64[num_values]: sums / 2^32 / nsamples per value row (nan where nothing was sampled), laid out
+        like the tallies of `marginals()`."""
+        t, n = self.rb_sums()
+        base, _ = self.graph.values()
+        raw = self.graph.raw
+        card = np.where(np.asarray(raw.var_dtype) == 0, 1, np.asarray(raw.var_cardinality)).astype(np.int64)
+        per_row = np.repeat(n.astype(np.float64), card)
+        assert len(per_row) == len(t) and np.array_equal(np.asarray(base, np.int64), np.cumsum(card) - card)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return t.astype(np.float64) / 4294967296.0 / per_row
+
     def assignments(self, chain):
         out = np.zeros(self.V, np.uint64)
         c = 0 if chain in (0, "free") else 1
@@ -396,9 +422,14 @@ class GibbsSampler:
         base, _ = self.graph.values()
         return t, n, base
 
-    def marginals_text(self):
+    def marginals_text(self, rao_blackwell=False):
+        """inference_result.out.text; rao_blackwell: the same rows from rb_sums() / 2^32 instead of the tallies."""
         raw = self.graph.raw
-        t, n = self.tallies()
+        if rao_blackwell:
+            t, n = self.rb_sums()
+            t = t.astype(np.float64) / 4294967296.0
+        else:
+            t, n = self.tallies()
         base, sparse = self.graph.values()
         out = []
         for v in range(self.V):

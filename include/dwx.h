@@ -336,6 +336,34 @@ int dwx_get_tallies(dwx_sampler *s, uint64_t *tallies, uint64_t *nsamples);
  *   dwx_clear_tallies    zeroes them with the tallies; DWX_BUF_RB is the device array. */
 int dwx_rb_enable(dwx_sampler *s, int on);
 int dwx_get_rb_sums(dwx_sampler *s, uint64_t *sums, uint64_t *nsamples);
+/* Posterior sample trace.  NO reference counterpart: the reference overwrites every assignment with the next
+ * sweep's and keeps counts only (sample_single_variable, src/gibbs_sampler.h:160-167), so neither a variable's
+ * draws as a sequence (split-R-hat, effective sample size: sampler_amd/diagnostics.py) nor a joint sample
+ * (co-occurrences, P(a and b)) can be had from it.  The trace is a ring, on the device, of the assignments of the
+ * inference chain (chain 1, the one dwx_sample_async advances) after each of the last `capacity` INFERENCE
+ * sweeps (dwx_sample_async, dwx_sample_n_async; never a learning sweep), packed: 1 bit per owned variable
+ * when no owned variable is categorical, else 1 byte.  Ghost variables are not traced.
+ *   dwx_trace_enable(s, capacity)  allocates the ring on first use (capacity x ceil(V_owned / 64) x 8 bytes, or
+ *                        capacity x ceil(V_owned / 8) x 8; DWX_E_NOMEM leaves the sampler usable, trace off);
+ *                        capacity 0 stops recording and keeps what is there; a different non-zero capacity
+ *                        reallocates and empties the ring; DWX_E_LIMIT when max_cardinality > 256.
+ *   dwx_trace_info       entries held, the capacity, and (sweep_ids[count], may be null) oldest first the
+ *                        value of the sweep counter each entry was drawn at -- the Philox counter word of that
+ *                        sweep (dwx_get_sweep before it ran): learning sweeps in between leave gaps.
+ *   dwx_trace_read       out[e * n_vids + i] = the dense value of variable vids[i] (REFERENCE numbering) in
+ *                        entry first_entry + e (0 = oldest), as dwx_get_assignments(s, 1, ...) would have
+ *                        returned it right after that sweep -- also for a variable the sweep does not sample
+ *                        (evidence without sample_evidence: the value it had).  vids == NULL: all owned variables,
+ *                        n_vids ignored.  The selection is gathered and unpacked on the device: only
+ *                        n_entries x n_vids bytes cross to the host.  DWX_E_INVALID when never enabled, on a
+ *                        range outside the entries held, on a ghost or unknown id.
+ *   dwx_clear_tallies    empties the trace with the tallies: while count <= capacity, the number of entries
+ *                        with value d equals tallies[row0 + d] for every sampled variable.
+ * With the trace off nothing is launched or allocated for it. */
+int dwx_trace_enable(dwx_sampler *s, uint32_t capacity_sweeps);
+int dwx_trace_info(dwx_sampler *s, uint64_t *count, uint64_t *capacity, uint64_t *sweep_ids);
+int dwx_trace_read(dwx_sampler *s, uint64_t first_entry, uint64_t n_entries, const uint64_t *vids, uint64_t n_vids,
+                   uint8_t *out);
 /* assignments_free (chain 0) / assignments_evid (chain 1), original variable order */
 int dwx_get_assignments(dwx_sampler *s, int chain, uint64_t *out);
 int dwx_set_assignments(dwx_sampler *s, int chain, const uint64_t *in);
@@ -366,9 +394,14 @@ enum {
   DWX_BUF_SORTED_RECORDS_PLAN = 8, /* layout / of the current plan level's own (8 bytes per record;
                                       null / 0 bytes when there is none): the device build
                                       (device_build.hip) is checked against the host builder's bytes  */
-  DWX_BUF_RB = 9            /* uint64[num_values] in device order, like DWX_BUF_TALLIES: the
+  DWX_BUF_RB = 9,           /* uint64[num_values] in device order, like DWX_BUF_TALLIES: the
                                Rao-Blackwellised sums (2^-32 fixed point; dwx_rb_enable); null / 0
                                bytes when never enabled.  Replicas sum it with a 64-bit integer sum  */
+  DWX_BUF_TRACE = 10        /* the sample trace's ring (dwx_trace_enable), in the library's OWN device
+                               layout (packed planes in device order, a ring) -- not for interpretation,
+                               read it through dwx_trace_read; here so that its footprint can be seen:
+                               capacity x ceil(V_owned / 64) x 8 bytes on an all-boolean graph, no
+                               other padding.  Null / 0 bytes when never enabled  */
 };
 int dwx_device_buffer(dwx_sampler *s, int which, void **dev_ptr, uint64_t *nbytes);
 /* Copy between host memory and a device pointer obtained from dwx_device_buffer /

@@ -512,6 +512,72 @@ halo_unpack_kernel(const uint32_t *pos, uint32_t n, uint32_t *assign_free, uint3
   }
 }
 
+// Sample trace (dwx_trace_enable; NO reference counterpart: the reference only counts the drawn values,
+// src/gibbs_sampler.h:160-167, and overwrites every assignment with the next).  The ring holds `cap` planes of
+// `words` 8-byte words; a plane is the inference chain's assignment of owned positions [0, n) in device order,
+// BITS = 1: bit (p & 63) of word p >> 6 (all-boolean graph: lane <-> position, a wave's 64 values are one
+// ballot, one 8-byte store per wave), BITS = 8: byte p (four values per 32-bit store).
+// trace_pack_kernel writes the CURRENT assign_evid into planes slot0, slot0 + 1, ... (mod cap), n_planes of
+// them: one plane after every single inference sweep, whatever kernels the sweep took.  unsampled_only: the
+// positions an inference sweep draws (not evidence, or OPT_SAMPLE_EVIDENCE) are written as 0 -- the planes a
+// one-launch run of sweeps (sweep8_kernel<MULTI, TRACE>) is about to fill: its draws are ADDED as disjoint bits
+// (BITS = 1) or stored over the zero bytes (BITS = 8), the unsampled positions hold their value in every plane.
+template <int BITS>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+trace_pack_kernel(const uint32_t *assign_evid, const uint32_t *v_meta, uint32_t n, uint32_t unsampled_only,
+                  uint32_t sample_evidence, unsigned long long *ring, uint32_t words, uint32_t cap, uint32_t slot0,
+                  uint32_t n_planes) {
+  const uint32_t stride = gridDim.x * blockDim.x;
+  auto keep = [&](uint32_t p) {
+    return !unsampled_only || (!sample_evidence && (v_meta[p] & VM_EVIDENCE));
+  };
+  if (BITS == 1) {
+    const uint32_t n_round = (n + blockDim.x - 1) / blockDim.x * blockDim.x;   // (whole workgroups ballot together)
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_round; p += stride) {
+      const bool one = p < n && keep(p) && assign_evid[p] != 0;
+      const unsigned long long m = DWX_BALLOT(one);
+      if ((threadIdx.x & 63u) == 0 && p < n) {   // (p: the wave's first position, a multiple of 64)
+        uint32_t slot = slot0;
+        for (uint32_t j = 0; j < n_planes; ++j) {
+          ring[(size_t)slot * words + (p >> 6)] = m;
+          if (++slot == cap) slot = 0;
+        }
+      }
+    }
+  } else {
+    const uint32_t n4 = (n + 3u) / 4u;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+      uint32_t packed = 0;
+#pragma unroll
+      for (uint32_t b = 0; b < 4u; ++b) {
+        const uint32_t p = 4u * i + b;
+        if (p < n && keep(p)) packed |= (assign_evid[p] & 255u) << (8u * b);
+      }
+      uint32_t slot = slot0;
+      for (uint32_t j = 0; j < n_planes; ++j) {
+        ((uint32_t *)(ring + (size_t)slot * words))[i] = packed;
+        if (++slot == cap) slot = 0;
+      }
+    }
+  }
+}
+
+// dwx_trace_read: out[e * n_pos + i] = the value of position pos[i] in entry e of the ring, entry 0 at plane
+// slot0 (the oldest entry asked for), one byte each.  pos was translated once per call on the host
+// (CompiledGraph::pos, as dwx_graph_get_positions); only the selection crosses to the host.
+template <int BITS>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+trace_gather_kernel(const unsigned long long *ring, uint32_t words, uint32_t cap, uint32_t slot0, uint32_t n_entries,
+                    const uint32_t *pos, uint64_t n_pos, unsigned char *out) {
+  const uint64_t total = (uint64_t)n_entries * n_pos, stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += stride) {
+    const uint64_t e = j / n_pos, i = j - e * n_pos;
+    const uint32_t slot = (uint32_t)(((uint64_t)slot0 + e) % cap), p = pos[i];
+    const unsigned long long *plane = ring + (size_t)slot * words;
+    out[j] = BITS == 1 ? (unsigned char)((plane[p >> 6] >> (p & 63u)) & 1ull) : ((const unsigned char *)plane)[p];
+  }
+}
+
 // test hook: the raw Philox4x32-10 block function and the two uniforms drawn from it, on the
 // device (Random123 known-answer vectors; tests/test_philox_kat.py)
 __global__ void test_philox_kernel(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,

@@ -275,6 +275,12 @@ struct KernelParams {
   // the inference draws decide on, laid out like `tally`; null = off.  Only read by the RB builds of the
   // inference kernels (last member: no other kernel's argument offsets move).
   unsigned long long *rb;
+  // Sample trace (dwx_trace_enable): the ring of packed assignment planes, trace_words 8-byte
+  // words per plane, trace_cap planes.  Only read by the TRACE builds of sweep8_kernel<MULTI>: sweep k of the
+  // launch, k >= trace_skip, writes plane (trace_slot0 + k - trace_skip) mod trace_cap.  trace_bits: 1 (a bit
+  // per position, all-boolean graph) or 8 (a byte per position).  Single sweeps are packed by trace_pack_kernel.
+  unsigned long long *trace;
+  uint32_t trace_words, trace_cap, trace_slot0, trace_skip, trace_bits;
 };
 
 // A split learning sweep of a few-weights graph as ONE persistent launch (persist_learn8_kernel,

@@ -43,6 +43,7 @@ const FlagSpec kFlags[] = {
     {"", "learn_non_evidence", false}, {"", "noise_aware", false},
     {"", "device", true}, {"", "seed", true}, {"", "step_cap", true}, {"", "plan_layouts", true},
     {"", "gpus", true}, {"", "devices", true}, {"", "comm", true}, {"", "rao_blackwell", false},
+    {"", "trace", true}, {"", "trace_vars", true},
 };
 
 const FlagSpec *find_flag(const std::string &tok) {
@@ -179,6 +180,8 @@ CmdLine parse_cmdline(int argc, const char *const argv[]) {
     else if (n == "plan_layouts") { if (need_u()) a.plan_layouts = (int)u; }
     else if (n == "gpus") { if (need_u()) a.gpus = (int)u; }
     else if (n == "rao_blackwell") a.rao_blackwell = true;
+    else if (n == "trace") { if (need_u()) a.trace = u; }
+    else if (n == "trace_vars") a.trace_vars = val;
     else if (n == "comm") {
       if (val != "rccl" && val != "host") { ++a.num_errors; err << "PARSE ERROR: Argument: --comm\n             must be rccl or host\n"; }
       a.comm = val;
@@ -237,6 +240,7 @@ std::ostream &operator<<(std::ostream &stream, const CmdLine &args) {
       DWX_ROW("device (HIP)", device),
       DWX_ROW("seed", seed),
       {"rao_blackwell", [](std::ostream &o, const CmdLine &a) { o << a.rao_blackwell; }, [](const CmdLine &a) { return a.rao_blackwell; }},
+      {"trace", [](std::ostream &o, const CmdLine &a) { o << a.trace; }, [](const CmdLine &a) { return a.trace > 0; }},
   };
 #undef DWX_ROW
 #undef DWX_ROW_LIST
@@ -904,6 +908,48 @@ double now() {
 }
 }  // namespace
 
+// --trace: everything the ring holds, read through dwx_trace_read (the selection is unpacked on the device)
+void dump_trace_to_file(const std::string &path, dwx_sampler *sampler, uint64_t n_variables, const std::string &vars_file) {
+  auto ok = [](int rc) { if (rc != DWX_OK) throw std::runtime_error(dwx_last_error()); };
+  std::vector<uint64_t> vids;
+  if (!vars_file.empty()) {
+    std::ifstream in(vars_file);
+    if (!in) throw std::runtime_error("--trace_vars: cannot open " + vars_file);
+    std::string line;
+    while (getline(in, line)) {
+      uint64_t v = 0;
+      const size_t b = line.find_first_not_of(" \t\r"), e = line.find_last_not_of(" \t\r");
+      if (b == std::string::npos) continue;
+      if (!to_u64(line.substr(b, e - b + 1), v))
+        throw std::runtime_error("--trace_vars: not a variable id: '" + line + "'");
+      vids.push_back(v);
+    }
+  } else {
+    vids.resize(n_variables);
+    for (uint64_t v = 0; v < n_variables; ++v) vids[v] = v;
+  }
+  uint64_t count = 0, cap = 0;
+  ok(dwx_trace_info(sampler, &count, &cap, nullptr));
+  std::vector<uint64_t> ids(count);
+  if (count) ok(dwx_trace_info(sampler, nullptr, nullptr, ids.data()));
+  std::vector<uint8_t> vals(count * vids.size());
+  if (count && !vids.empty()) ok(dwx_trace_read(sampler, 0, count, vids.data(), vids.size(), vals.data()));
+  std::string s = "# sweeps:";
+  for (uint64_t e = 0; e < count; ++e) s += " " + std::to_string(ids[e]);
+  s += "\n";
+  for (size_t i = 0; i < vids.size(); ++i) {
+    s += std::to_string(vids[i]);
+    for (uint64_t e = 0; e < count; ++e) {
+      s += e ? ' ' : '\t';
+      s += std::to_string((unsigned)vals[e * vids.size() + i]);
+    }
+    s += '\n';
+  }
+  std::ofstream f(path, std::ios::binary);
+  f.write(s.data(), (std::streamsize)s.size());
+  if (!f) throw std::runtime_error("cannot write " + path);
+}
+
 // Graph-compile options of a `dw gibbs` run.  Ordering the variables of an all-unary graph by the
 // weight of their first record makes a sweep ~5 % faster and the host-side build
 // much slower -- the records are then gathered in a random order: 10 s of a 42 s run at config 5's
@@ -1093,6 +1139,11 @@ int gibbs(const CmdLine &args) {
     t_total = now();
     // --rao_blackwell: the inference sweeps also sum the conditionals their draws decide on (include/dwx.h)
     if (args.rao_blackwell) ok(dwx_rb_enable(sampler, 1));
+    // --trace N: the inference sweeps also keep the last N joint assignments on the device (include/dwx.h)
+    if (args.trace) {
+      if (args.trace > 0xFFFFFFFFull) throw std::runtime_error("--trace: at most 4294967295 sweeps");
+      ok(dwx_trace_enable(sampler, (uint32_t)args.trace));
+    }
     ok(dwx_clear_tallies(sampler));
     for (uint64_t e = 0; e < args.n_inference_epoch; ++e) {
       if (progress) {
@@ -1147,6 +1198,15 @@ int gibbs(const CmdLine &args) {
       phase("dwx_get_tallies");
       dump_marginals_to_file(fn, lg, args.should_sample_evidence, base.data(), sparse.data(), tallies.data(), nsamples.data(), rb);
       phase("dump marginals");
+      if (args.trace) {
+        // --trace N [--trace_vars FILE]: "# sweeps: id id ..." (the sweep counter of each kept sweep, oldest
+        // first), then per selected variable "vid <tab> value value ..." in the same order.  No reference
+        // counterpart (its sweeps overwrite the assignment, src/gibbs_sampler.h:160-167).
+        fn = args.output_folder + "/inference_result.out.trace.text";
+        std::cout << "DUMPING... TEXT    : " << fn << std::endl;
+        dump_trace_to_file(fn, sampler, V, args.trace_vars);
+        phase("dump trace");
+      }
       if (progress) {
         // the reference's closing calibration table (InferenceResult::show_marginal_histogram,
         // src/inference_result.cc:171-209): how many sampled (variable, value) rows have their

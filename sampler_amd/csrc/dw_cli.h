@@ -44,6 +44,9 @@ struct CmdLine {
   std::vector<int> devices;     // --devices a,b,...: the ranks' HIP devices (default 0..N-1)
   std::string comm = "rccl";    // --comm rccl | host (host-staged sums: a test stand-in)
   bool rao_blackwell = false;   // --rao_blackwell: the marginals are the Rao-Blackwellised estimate (dwx_rb_enable)
+  uint64_t trace = 0;           // --trace N: keep the last N inference sweeps' joint assignments (dwx_trace_enable) and
+  std::string trace_vars;       // write them, for --trace_vars FILE's variables (one id per line; default: all), to
+                                // <out>/inference_result.out.trace.text.  Single rank only.
   int num_errors = 0;
   std::string error_text;
 };
@@ -96,6 +99,9 @@ void dump_weights_to_file(const std::string &path, const std::vector<double> &w)
 void dump_marginals_to_file(const std::string &path, const LoadedGraph &g, bool sample_evidence,
                             const uint64_t *var_val_base, const uint64_t *value_sparse,
                             const uint64_t *tallies, const uint64_t *nsamples, bool rao_blackwell = false);
+
+// --trace (dw_cli.cc): "# sweeps: id ..." then "vid <tab> v v ..." per selected variable, oldest sweep first
+void dump_trace_to_file(const std::string &path, dwx_sampler *sampler, uint64_t n_variables, const std::string &vars_file);
 
 // graph-compile options of a run (dw_cli.cc: the weight order of the variables only for long runs)
 dwx_compile_opts compile_opts_for(const CmdLine &args);

@@ -733,6 +733,11 @@ void Rank::run() {
 int gibbs_multi(const CmdLine &args) {
   int exit_code = 0;
   dwx_graph *replica_graph = nullptr;
+  // the sample trace is one sampler's (include/dwx.h): per-rank traces of shards or replicas are not written
+  if (args.trace) {
+    std::cerr << "dw: --trace is not supported with --gpus or -c (n_datacopy): run a single rank" << std::endl;
+    return 2;
+  }
   try {
     const bool replicas = args.gpus < 1;           // -c N without --gpus: the reference's n_datacopy
     int n = replicas ? (int)args.n_datacopy : args.gpus;

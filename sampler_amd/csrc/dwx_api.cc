@@ -168,7 +168,14 @@ struct dwx_sampler {
   // Rao-Blackwellised marginals (dwx_rb_enable; tile_walk.h rb_*): [R] 32.32 fixed-point sums, device order
   unsigned long long *d_rb = nullptr;   // allocated by the first enable
   bool rb_on = false;                   // inference sweeps run the RB builds of their kernels and accumulate
-  std::set<std::pair<const void *, size_t>> rb_lds_allowed;   // RB builds whose dynamic LDS size is already allowed
+  std::set<std::pair<const void *, size_t>> rb_lds_allowed;   // RB / TRACE builds whose dynamic LDS size is already allowed
+  // Sample trace (dwx_trace_enable): a ring of the last trace_cap inference sweeps' assignments of
+  // the inference chain, packed (aux_kernels.h: trace_pack_kernel), in device order
+  unsigned long long *d_trace = nullptr;   // [trace_cap][trace_words], allocated by the first enable
+  uint32_t trace_cap = 0, trace_words = 0, trace_bits = 0;   // planes; 8-byte words per plane; 1 or 8 bits per position
+  uint32_t trace_next = 0, trace_count = 0;                  // the plane the next sweep writes; entries held
+  bool trace_on = false;                   // inference sweeps record
+  std::vector<uint64_t> trace_ids;         // [trace_cap] by plane: the sweep counter its entry was drawn at
   long long *d_pot = nullptr;       // [V] fixed-point sums by device position (allocated on first use)
   int pot_alloc = 0;                // 0 not tried yet, 1 d_pot allocated, -1 no cache (not eligible, DWX_NO_POT_CACHE, no memory)
   std::vector<uint8_t> pot_valid;   // [launches] one sweep stored every query tile's sum, no weight changed since
@@ -273,7 +280,7 @@ struct dwx_sampler {
     rt::dfree(d_grad32); rt::dfree(d_pack_bad);
     rt::dfree(d_edges); rt::dfree(d_edges8); rt::dfree(d_vifs); rt::dfree(d_assign_free); rt::dfree(d_assign_evid);
     rt::dfree(d_tally); rt::dfree(d_weights); rt::dfree(d_w32); rt::dfree(d_w_init); rt::dfree(d_terms); rt::dfree(d_delta);
-    rt::dfree(d_pot); rt::dfree(d_rb);
+    rt::dfree(d_pot); rt::dfree(d_rb); rt::dfree(d_trace);
     rt::dfree(d_w_fixed); rt::dfree(d_grad); rt::dfree(d_persist_rows); rt::dfree(d_persist_bar);
     rt::dfree(d_gbuf[1]); rt::dfree(d_gbuf[2]); rt::dfree(d_wbuf64[0]); rt::dfree(d_wbuf64[1]); rt::dfree(d_wbuf32[0]); rt::dfree(d_wbuf32[1]);
     for (int i = 0; i < 2; ++i) { if (side[i]) rt::stream_destroy(side[i]); if (ev_join[i]) rt::event_destroy(ev_join[i]); }
@@ -312,7 +319,8 @@ void rb_allow_lds(dwx_sampler *s, K kernel, size_t lds) {
 // multi (inference of a graph without degree-binned variables): P.n_sweeps sweeps per launch
 // covered (if given): the end of the gap-free run of weight-sorted super-tiles that starts at t0 (t0: none)
 // RB (inference only): the builds that add every draw's conditional to P.rb (dwx_rb_enable)
-template <bool LEARN, bool RB = false>
+// TRACE (multi only): the builds that write every sweep's draws to the sample trace (dwx_trace_enable)
+template <bool LEARN, bool RB = false, bool TRACE = false>
 uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, uint32_t t1, const bool multi = false,
                       uint32_t *covered = nullptr) {
   static_assert(!(LEARN && RB), "Rao-Blackwellised sums: inference sweeps only");
@@ -362,18 +370,18 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
   // nothing.  The persistent grid is the one sized from the plain build's occupancy: a build that keeps fewer
   // workgroups resident runs the surplus ones after the first leave -- correct, the tiles are strided.)
   auto go = [&](auto kernel) {
-    if (RB) rb_allow_lds(s, kernel, lds);
+    if (RB || TRACE) rb_allow_lds(s, kernel, lds);
     rt::launch(kernel, grid, BLOCK_THREADS, lds, s->stream, P);
   };
 
   if constexpr (!LEARN) {
     if (multi) {   // (only asked for on compact-record graphs, never on the terms table)
       constexpr int RP = (int)ROWPTR_UNROLL;
-      if (s->rp_cat) go(sweep8_kernel<false, 6, false, RPC, true, RB>);
+      if (s->rp_cat) go(sweep8_kernel<false, 6, false, RPC, true, RB, TRACE>);
       else switch (s->stage_k) {
-        case 3: go(sweep8_kernel<false, 3, false, RP, true, RB>); break;
-        case 6: go(sweep8_kernel<false, 6, false, RP, true, RB>); break;
-        default: go(sweep8_kernel<false, 12, false, RP, true, RB>); break;
+        case 3: go(sweep8_kernel<false, 3, false, RP, true, RB, TRACE>); break;
+        case 6: go(sweep8_kernel<false, 6, false, RP, true, RB, TRACE>); break;
+        default: go(sweep8_kernel<false, 12, false, RP, true, RB, TRACE>); break;
       }
       ++launches;
       return;
@@ -530,6 +538,29 @@ bool multi_sweep_graph(const dwx_sampler *s) {
          !getenv("DWX_NO_MULTI_SWEEP");
 }
 
+// Sample trace: pack the inference chain's current assignment into n_planes planes of the ring from trace_next on
+// (unsampled_only: only the positions inference sweeps do not draw, the others cleared -- the planes a one-launch
+// run is about to fill), and enter sweeps [first_id, first_id + n_planes) as the ring's newest entries.
+void trace_pack(dwx_sampler *s, uint64_t first_id, uint32_t n_planes, bool unsampled_only) {
+  const CompiledGraph &c = *s->cg;
+  const uint32_t n = (uint32_t)c.Vo;
+  if (n) {
+    const uint32_t items = s->trace_bits == 1 ? n : (n + 3u) / 4u;
+    const unsigned grid = std::min<unsigned>((items + BLOCK_THREADS - 1) / BLOCK_THREADS, 256u * 16u);
+    auto go = [&](auto kernel) {
+      rt::launch(kernel, grid, BLOCK_THREADS, 0, s->stream, (const uint32_t *)s->d_assign_evid, (const uint32_t *)s->d_v_meta,
+                 n, unsampled_only ? 1u : 0u, s->opts.sample_evidence ? 1u : 0u, s->d_trace, s->trace_words, s->trace_cap,
+                 s->trace_next, n_planes);
+    };
+    if (s->trace_bits == 1) go(trace_pack_kernel<1>); else go(trace_pack_kernel<8>);
+  }
+  for (uint32_t j = 0; j < n_planes; ++j) {
+    s->trace_ids[s->trace_next] = first_id + j;
+    s->trace_next = s->trace_next + 1 == s->trace_cap ? 0 : s->trace_next + 1;
+    s->trace_count = std::min(s->trace_count + 1, s->trace_cap);
+  }
+}
+
 void enqueue_inference_multi(dwx_sampler *s, uint32_t n) {
   const CompiledGraph &c = *s->cg;
   rt::set_device(s->device);
@@ -544,10 +575,23 @@ void enqueue_inference_multi(dwx_sampler *s, uint32_t n) {
     rt::event_record(sp.a, s->stream);
   }
   uint32_t launches = 0;
+  // the sample trace: the last min(n, capacity) sweeps of the launch write their planes themselves
+  // (sweep8_kernel<MULTI, TRACE>), over what trace_pack_kernel leaves there: the unsampled positions' values
+  P.trace = nullptr;
+  if (s->trace_on) {
+    const uint32_t m = std::min(n, s->trace_cap);
+    P.trace = s->d_trace; P.trace_words = s->trace_words; P.trace_cap = s->trace_cap; P.trace_bits = s->trace_bits;
+    P.trace_slot0 = s->trace_next; P.trace_skip = n - m;
+    trace_pack(s, s->sweep + (n - m), m, true);
+    ++launches;
+  }
   for (size_t l = 0; l + 1 < c.launch_off.size(); ++l) {
+    const uint32_t t0 = c.launch_tile[l];
     const uint32_t t1 = s->opts.sample_evidence ? c.launch_tile[l + 1] : c.launch_query_tile_end[l];
-    launches += P.rb ? launch_tiles<false, true>(s, P, l, c.launch_tile[l], t1, true)
-                     : launch_tiles<false>(s, P, l, c.launch_tile[l], t1, true);
+    launches += P.trace ? (P.rb ? launch_tiles<false, true, true>(s, P, l, t0, t1, true)
+                                : launch_tiles<false, false, true>(s, P, l, t0, t1, true))
+                        : (P.rb ? launch_tiles<false, true>(s, P, l, t0, t1, true)
+                                : launch_tiles<false>(s, P, l, t0, t1, true));
   }
   if (s->timing) {
     rt::event_record(sp.b, s->stream);
@@ -625,6 +669,11 @@ void enqueue_inference(dwx_sampler *s) {
     // valid for launch l only if sorted_sweep_kernel stored the sum of EVERY query tile (none took the
     // tile sweep, the terms table or a degree-bin kernel)
     if (P.pot && c.launch_query_tile_end[l] > c.launch_tile[l] && covered >= c.launch_query_tile_end[l]) s->pot_valid[l] = 1;
+  }
+  // the sample trace: one pass over the assignment the sweep left, whatever kernels it took
+  if (s->trace_on) {
+    trace_pack(s, s->sweep, 1, false);
+    ++launches;
   }
   if (s->timing) {
     rt::event_record(sp.b, s->stream);
@@ -2486,6 +2535,7 @@ int dwx_clear_tallies(dwx_sampler *s) {
     rt::set_device(s->device);
     rt::dmemset(s->d_tally, 0, s->cg->R * 4, s->stream);
     if (s->d_rb) rt::dmemset(s->d_rb, 0, s->cg->R * 8, s->stream);
+    s->trace_next = s->trace_count = 0;   // (the planes are overwritten whole before they are read again)
     s->infer_sweeps = 0;
   });
 }
@@ -2532,6 +2582,93 @@ int dwx_get_rb_sums(dwx_sampler *s, uint64_t *sums, uint64_t *nsamples) {
   });
   if (rc != DWX_OK) return rc;
   return nsamples ? dwx_get_tallies(s, nullptr, nsamples) : DWX_OK;
+}
+
+int dwx_trace_enable(dwx_sampler *s, uint32_t capacity_sweeps) {
+  if (!s) return fail(DWX_E_INVALID, "null sampler");
+  if (!capacity_sweeps) { s->trace_on = false; return DWX_OK; }
+  const CompiledGraph &c = *s->cg;
+  if (c.max_card > 256) return fail(DWX_E_LIMIT, "the sample trace holds a byte per variable: cardinalities up to 256");
+  if (!s->d_trace || capacity_sweeps != s->trace_cap) {
+    bool boolean = true;
+    for (uint64_t p = 0; p < c.Vo && boolean; ++p) boolean = !(c.v_meta[p] & VM_CATEGORICAL);
+    const uint32_t bits = boolean ? 1u : 8u;
+    // a plane: whole 8-byte words, ceil(Vo / 64) of them at a bit per position, ceil(Vo / 8) at a byte; no other padding
+    const uint64_t words = bits == 1 ? (c.Vo + 63) / 64 : (c.Vo + 7) / 8;
+    const size_t bytes = std::max<size_t>((size_t)capacity_sweeps * words * 8, 8);
+    void *p = nullptr;
+    int rc = guarded([&]() {
+      rt::set_device(s->device);
+      rt::stream_sync(s->stream);   // (a sweep in flight may still write the ring about to be freed)
+      rt::dfree(s->d_trace);
+      s->d_trace = nullptr; s->trace_on = false; s->trace_cap = s->trace_next = s->trace_count = 0;
+#ifdef DWX_EMU
+      p = rt::dmalloc(bytes);
+#else
+      p = rt::try_dmalloc(bytes);
+#endif
+      if (p) rt::dmemset(p, 0, bytes, s->stream);
+    });
+    if (rc != DWX_OK) return rc;
+    if (!p) return fail(DWX_E_NOMEM, "no device memory for the sample trace (capacity x ceil(V / 64) x 8 bytes, or x V bytes)");
+    s->d_trace = (unsigned long long *)p;
+    s->trace_cap = capacity_sweeps; s->trace_words = (uint32_t)words; s->trace_bits = bits;
+    s->trace_ids.assign(capacity_sweeps, 0);
+  }
+  s->trace_on = true;
+  return DWX_OK;
+}
+
+int dwx_trace_info(dwx_sampler *s, uint64_t *count, uint64_t *capacity, uint64_t *sweep_ids) {
+  if (!s) return fail(DWX_E_INVALID, "null sampler");
+  if (count) *count = s->trace_count;
+  if (capacity) *capacity = s->trace_cap;
+  if (sweep_ids)
+    for (uint32_t e = 0; e < s->trace_count; ++e)
+      sweep_ids[e] = s->trace_ids[(s->trace_next + s->trace_cap - s->trace_count + e) % s->trace_cap];
+  return DWX_OK;
+}
+
+int dwx_trace_read(dwx_sampler *s, uint64_t first_entry, uint64_t n_entries, const uint64_t *vids, uint64_t n_vids,
+                   uint8_t *out) {
+  if (!s) return fail(DWX_E_INVALID, "null sampler");
+  if (!s->d_trace) return fail(DWX_E_INVALID, "the sample trace was never enabled (dwx_trace_enable)");
+  if (first_entry > s->trace_count || n_entries > s->trace_count - first_entry)
+    return fail(DWX_E_INVALID, "entries outside the sample trace (dwx_trace_info: count)");
+  const CompiledGraph &c = *s->cg;
+  if (!vids) n_vids = c.Vo;
+  if (n_entries > 0xFFFFFFFFull) return fail(DWX_E_INVALID, "entries outside the sample trace");
+  if (!n_entries || !n_vids) return DWX_OK;
+  if (!out) return fail(DWX_E_INVALID, "null argument");
+  std::vector<uint32_t> pos(n_vids);
+  for (uint64_t i = 0; i < n_vids; ++i) {
+    const uint64_t v = vids ? vids[i] : i;
+    if (v >= c.V) return fail(DWX_E_INVALID, "variable id out of range");
+    pos[i] = c.pos[v];
+    if (pos[i] >= c.Vo) return fail(DWX_E_INVALID, "ghost variables are not traced");
+  }
+  return guarded([&]() {
+    rt::set_device(s->device);
+    const uint64_t total = n_entries * n_vids;
+    uint32_t *d_pos = upload(pos, s->stream);
+    unsigned char *d_out = nullptr;
+    try {
+      d_out = (unsigned char *)rt::dmalloc(total);
+      const uint32_t slot0 = (uint32_t)((s->trace_next + s->trace_cap - s->trace_count + first_entry) % s->trace_cap);
+      const unsigned grid = (unsigned)std::min<uint64_t>((total + BLOCK_THREADS - 1) / BLOCK_THREADS, 256u * 16u);
+      auto go = [&](auto kernel) {
+        rt::launch(kernel, grid, BLOCK_THREADS, 0, s->stream, (const unsigned long long *)s->d_trace, s->trace_words,
+                   s->trace_cap, slot0, (uint32_t)n_entries, (const uint32_t *)d_pos, n_vids, d_out);
+      };
+      if (s->trace_bits == 1) go(trace_gather_kernel<1>); else go(trace_gather_kernel<8>);
+      rt::d2h(out, d_out, total, s->stream);
+      rt::stream_sync(s->stream);
+    } catch (...) {
+      rt::dfree(d_pos); rt::dfree(d_out);
+      throw;
+    }
+    rt::dfree(d_pos); rt::dfree(d_out);
+  });
 }
 
 int dwx_get_tallies(dwx_sampler *s, uint64_t *tallies, uint64_t *nsamples) {
@@ -2604,6 +2741,7 @@ int dwx_device_buffer(dwx_sampler *s, int which, void **dev_ptr, uint64_t *nbyte
     case DWX_BUF_ASSIGN_EVID: *dev_ptr = s->d_assign_evid; *nbytes = c.V * 4; break;
     case DWX_BUF_TALLIES: *dev_ptr = s->d_tally; *nbytes = c.R * 4; break;
     case DWX_BUF_RB: *dev_ptr = s->d_rb; *nbytes = s->d_rb ? c.R * 8 : 0; break;
+    case DWX_BUF_TRACE: *dev_ptr = s->d_trace; *nbytes = s->d_trace ? (uint64_t)s->trace_cap * s->trace_words * 8 : 0; break;
     case DWX_BUF_TSTATIC: {
       auto it = s->levels.find(1);
       *dev_ptr = it == s->levels.end() ? nullptr : it->second->d_t_static;

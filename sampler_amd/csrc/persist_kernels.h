@@ -188,7 +188,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS, DWX_S8_LEARN_WG) sweep8_merged_
       for (uint32_t i = threadIdx.x; i < 2u * W; i += BLOCK_THREADS) M.zero[i] = 0;
     __syncthreads();
   };
-  sweep8_body<true, K, false, RP, false, true, ONE, false, decltype(update)>(P, s_lw32, update);
+  sweep8_body<true, K, false, RP, false, true, ONE, false, false, decltype(update)>(P, s_lw32, update);
 }
 
 }  // namespace dwx

@@ -572,12 +572,13 @@ __global__ void __launch_bounds__(BLOCK_THREADS, WIDE ? (K <= 6 ? ((TV & TV_TERM
 // kernel's weight update: its own loads then return under the record stream's instead of before it).
 struct NoPrologue { DWX_DEV void operator()() const {} };
 template <bool LEARN, int K, bool TAB = false, int RP = (int)ROWPTR_UNROLL, bool MULTI = false, bool LW = false,
-          bool ONE = false, bool RB = false, class Pre = NoPrologue>
+          bool ONE = false, bool RB = false, bool TRACE = false, class Pre = NoPrologue>
 DWX_DEV void sweep8_body(const KernelParams &P, const float *lw32, Pre pre_fn = Pre()) {
   static_assert(!(LEARN && TAB), "the terms table serves inference sweeps only");
   static_assert(!MULTI || (!LEARN && !TAB), "several sweeps per launch: the gathering inference build");
   static_assert(!LW || (LEARN && !TAB && !MULTI), "LDS weights: the learning build");
   static_assert(!RB || !LEARN, "Rao-Blackwellised sums: inference builds");
+  static_assert(!TRACE || MULTI, "sample trace: written in-sweep by the one-launch build only (else: trace_pack_kernel)");
   DWX_DYN_LDS(dyn_lds);
   uint32_t *s_rowptr = (uint32_t *)dyn_lds;
   double *s_pot = (double *)(dyn_lds + P.lds_pot_off);
@@ -689,13 +690,15 @@ DWX_DEV void sweep8_body(const KernelParams &P, const float *lw32, Pre pre_fn = 
         TileView T{s_rowptr, d.r0, s_edges, d.e0, s_w, s_agg, P.lds_pot_off ? s_pot : nullptr};
         const uint32_t n = P.n_sweeps;
         const uint32_t S = (n >= MULTI_SLICE_MIN_SWEEPS && d.nv < BLOCK_THREADS) ? MULTI_SLICES : 1u;   // uniform
-        if (S == 1u) {   // (its own call: the loop over the sweeps keeps scalar bounds)
-          if (t < d.nv) infer_variable_multi<W_TERMS, true, RB>(P, T, d.v0 + t, pre, 0u, n, true);
+        if (TRACE && P.trace_bits == 1u) {   // (uniform; all-boolean graph: a ballot per sweep, never sliced)
+          infer_bool_multi_trace<W_TERMS, true, RB>(P, T, d.v0 + t, pre, n, t < d.nv);
+        } else if (S == 1u) {   // (its own call: the loop over the sweeps keeps scalar bounds)
+          if (t < d.nv) infer_variable_multi<W_TERMS, true, RB, TRACE>(P, T, d.v0 + t, pre, 0u, n, true);
         } else for (uint32_t item = t; item < S * d.nv; item += BLOCK_THREADS) {
           const uint32_t sl = item / d.nv, var = item - sl * d.nv;
           const VarPre vp = var == t ? pre : load_var_pre<false, false>(P, d.v0 + var);
           const uint32_t k_lo = (uint32_t)((uint64_t)n * sl / S), k_hi = (uint32_t)((uint64_t)n * (sl + 1) / S);
-          infer_variable_multi<W_TERMS, true, RB>(P, T, d.v0 + var, vp, k_lo, k_hi, sl + 1 == S);
+          infer_variable_multi<W_TERMS, true, RB, TRACE>(P, T, d.v0 + var, vp, k_lo, k_hi, sl + 1 == S);
         }
       }
     } else if (fits && t < d.nv) {
@@ -720,9 +723,11 @@ DWX_DEV void sweep8_body(const KernelParams &P, const float *lw32, Pre pre_fn = 
   }
   flush_accumulators(P, s_agg, t);
 }
-template <bool LEARN, int K, bool TAB = false, int RP = (int)ROWPTR_UNROLL, bool MULTI = false, bool RB = false>
+// TRACE (MULTI builds; dwx_trace_enable): every sweep's draws also go to the ring of packed planes (tile_walk.h)
+template <bool LEARN, int K, bool TAB = false, int RP = (int)ROWPTR_UNROLL, bool MULTI = false, bool RB = false,
+          bool TRACE = false>
 __global__ void __launch_bounds__(BLOCK_THREADS, TAB ? 4 : (LEARN ? DWX_S8_LEARN_WG : DWX_S8_INFER_WG)) sweep8_kernel(const KernelParams P) {
-  sweep8_body<LEARN, K, TAB, RP, MULTI, false, false, RB>(P, nullptr);
+  sweep8_body<LEARN, K, TAB, RP, MULTI, false, false, RB, TRACE>(P, nullptr);
 }
 
 // ---------------------------------------------------------------- weight-sorted super-tiles

@@ -951,7 +951,27 @@ DWX_DEV VarPre load_var_pre(const KernelParams &P, uint32_t p) {
 // than lanes cuts a long run of sweeps into slices, so that every lane draws: sweep8_kernel);
 // the slice that holds the last sweep stores the assignment.
 // RB: a sweep-invariant conditional is added (k_hi - k_lo) times in one add per value row.
-template <int WMODE, bool FIXED, bool RB = false>
+// TRACE (P.trace_bits == 8; dwx_trace_enable): sweep k's draw is stored as byte p of its plane of the ring, inside
+// the draw loop -- the only place where the draws of sweeps 0 .. n - 2 exist.  One byte per (variable, sweep), one
+// writer each: safe under the slicing.  (All-boolean graphs, a bit per position: infer_bool_multi_trace.)
+// The cursor over the planes of sweeps [k_lo, ...): sweep k >= P.trace_skip goes to plane
+// (trace_slot0 + k - trace_skip) mod trace_cap; the older sweeps of a run longer than the ring are not recorded.
+struct TraceCursor {
+  uint32_t slot = 0;
+  DWX_DEV void init(const KernelParams &P, uint32_t k_lo) {
+    const uint32_t k0 = k_lo > P.trace_skip ? k_lo : P.trace_skip;
+    slot = (uint32_t)(((uint64_t)P.trace_slot0 + (k0 - P.trace_skip)) % P.trace_cap);
+  }
+  DWX_DEV unsigned long long *plane(const KernelParams &P) const { return P.trace + (size_t)slot * P.trace_words; }
+  DWX_DEV void next(const KernelParams &P) { if (++slot == P.trace_cap) slot = 0; }
+};
+DWX_DEV void trace_byte(const KernelParams &P, TraceCursor &c, uint32_t k, uint32_t p, uint32_t value) {
+  if (k >= P.trace_skip) {
+    ((unsigned char *)c.plane(P))[p] = (unsigned char)value;
+    c.next(P);
+  }
+}
+template <int WMODE, bool FIXED, bool RB = false, bool TRACE = false>
 DWX_DEV void infer_variable_multi(const KernelParams &P, const TileView &T, uint32_t p, const VarPre pre,
                                   const uint32_t k_lo, const uint32_t k_hi, const bool store) {
   const uint32_t meta = pre.meta;
@@ -959,6 +979,8 @@ DWX_DEV void infer_variable_multi(const KernelParams &P, const TileView &T, uint
   const uint32_t card = meta >> VM_CARD_SHIFT, row0 = pre.row0;
   const uint64_t vid = P.vid_offset + pre.orig;
   uint32_t prop = 0;
+  TraceCursor tc;
+  if (TRACE) tc.init(P, k_lo);
   if (!(meta & VM_CATEGORICAL)) {
     double pp, pn;
     bool_potentials<WMODE, true, FIXED>(P, T, row0, P.assign_evid, p, pp, pn);
@@ -969,6 +991,7 @@ DWX_DEV void infer_variable_multi(const KernelParams &P, const TileView &T, uint
       philox_uniforms(P.seed, vid, P.sweep + k, A, B);
       prop = (A * scale < 1.0) ? 1u : 0u;
       count += prop;
+      if (TRACE) trace_byte(P, tc, k, p, prop);
     }
     if (count) atomicAdd(&P.tally[row0], count);
     if (RB && k_hi > k_lo) rb_add(P, row0, (unsigned long long)(k_hi - k_lo) * rb_bool_q(pp, pn));
@@ -1021,6 +1044,7 @@ DWX_DEV void infer_variable_multi(const KernelParams &P, const TileView &T, uint
         res = umin(res, card - 1);
         packed += 1ull << (res * 8u);
         prop = res;
+        if (TRACE) trace_byte(P, tc, k, p, prop);
       }
 #pragma unroll
       for (uint32_t d = 0; d < SMALL_CARD; ++d) cnt[d] += (uint32_t)(packed >> (d * 8u)) & 255u;
@@ -1036,9 +1060,56 @@ DWX_DEV void infer_variable_multi(const KernelParams &P, const TileView &T, uint
       philox_uniforms(P.seed, vid, P.sweep + k, A, B);
       prop = cat_draw<WMODE, true, RB>(P, T, row0, card, P.assign_evid, p, A);
       atomicAdd(&P.tally[row0 + prop], 1u);
+      if (TRACE) trace_byte(P, tc, k, p, prop);
     }
   }
   if (store) DWX_NT_STORE(prop, &P.assign_evid[p]);
+}
+
+// ... and the TRACE build's path of an all-boolean graph (P.trace_bits == 1): the same n draws of one boolean
+// variable per lane, lane <-> position, with ONE ballot per sweep and wave; one lane adds the wave's 64 bits into
+// the plane's word(s).  A tile's first position need not be a multiple of 64: the bits may straddle two words, and
+// two waves (of one or two workgroups) may share a word -- the host cleared the sampled positions' bits before the
+// launch (trace_pack_kernel, unsampled_only), so adding disjoint bits IS or-ing them, in any order.
+// EVERY thread of the workgroup runs the loop (in_tile: the lane has a variable; a lane without one, or with an
+// unsampled one, contributes zero bits): the ballot is reached by whole workgroups, and this path is never sliced
+// (sweep8_body) -- a slice would put one position's bits of different sweeps in different lanes.
+template <int WMODE, bool FIXED, bool RB>
+DWX_DEV void infer_bool_multi_trace(const KernelParams &P, const TileView &T, uint32_t p, const VarPre pre,
+                                    const uint32_t n, const bool in_tile) {
+  const bool active = in_tile && !((pre.meta & VM_EVIDENCE) && !(P.flags & OPT_SAMPLE_EVIDENCE));
+  const uint32_t row0 = pre.row0;
+  const uint64_t vid = P.vid_offset + pre.orig;
+  double pp = 0.0, pn = 0.0;
+  if (active) bool_potentials<WMODE, true, FIXED>(P, T, row0, P.assign_evid, p, pp, pn);
+  const double scale = 1.0 + exp(pn - pp);
+  const uint32_t lane = threadIdx.x & 63u, p0 = p - lane;   // p0: the position of the wave's lane 0
+  const uint32_t sh = p0 & 63u;
+  const size_t w = p0 >> 6;
+  TraceCursor tc;
+  tc.init(P, 0u);
+  uint32_t prop = 0, count = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    if (active) {
+      double A, B;
+      philox_uniforms(P.seed, vid, P.sweep + k, A, B);
+      prop = (A * scale < 1.0) ? 1u : 0u;
+      count += prop;
+    }
+    const unsigned long long m = DWX_BALLOT(active && prop);
+    if (k >= P.trace_skip) {
+      if (lane == 0 && m) {
+        unsigned long long *plane = tc.plane(P);
+        atomicAdd(&plane[w], m << sh);
+        if (sh && (m >> (64u - sh))) atomicAdd(&plane[w + 1], m >> (64u - sh));   // (nonzero: a position < V lies there)
+      }
+      tc.next(P);
+    }
+  }
+  if (!active) return;
+  if (count) atomicAdd(&P.tally[row0], count);
+  if (RB && n) rb_add(P, row0, (unsigned long long)n * rb_bool_q(pp, pn));
+  DWX_NT_STORE(prop, &P.assign_evid[p]);
 }
 
 // want_delta (learning, TILE_PULL tiles only): instead of scattering gradient atomics,

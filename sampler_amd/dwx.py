@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DWX_LIB") or os.path.join(HERE, "csrc", "libdwx.so")
 
 DWX_OK, DWX_E_INVALID, DWX_E_LIMIT, DWX_E_DEVICE, DWX_E_NOMEM = 0, -1, -2, -3, -4
-BUF_WEIGHTS, BUF_GRAD, BUF_ASSIGN_FREE, BUF_ASSIGN_EVID, BUF_TALLIES, BUF_TSTATIC, BUF_TSTATIC_PLAN, BUF_SORTED_RECORDS, BUF_SORTED_RECORDS_PLAN, BUF_RB = range(10)
+BUF_WEIGHTS, BUF_GRAD, BUF_ASSIGN_FREE, BUF_ASSIGN_EVID, BUF_TALLIES, BUF_TSTATIC, BUF_TSTATIC_PLAN, BUF_SORTED_RECORDS, BUF_SORTED_RECORDS_PLAN, BUF_RB, BUF_TRACE = range(11)
 
 # every symbol include/dwx.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -29,6 +29,7 @@ SYMBOLS = [
     "dwx_sgd_apply_async", "dwx_sgd_finish",
     "dwx_get_weights", "dwx_set_weights", "dwx_average_weights_async",
     "dwx_clear_tallies", "dwx_get_tallies", "dwx_rb_enable", "dwx_get_rb_sums",
+    "dwx_trace_enable", "dwx_trace_info", "dwx_trace_read",
     "dwx_get_assignments", "dwx_set_assignments", "dwx_get_sweep", "dwx_set_sweep",
     "dwx_device_buffer", "dwx_halo_create", "dwx_halo_destroy", "dwx_halo_buffer", "dwx_halo_message_bytes", "dwx_halo_pack_async",
     "dwx_halo_unpack_async", "dwx_stream", "dwx_kernel_time", "dwx_kernel_time_reset",
@@ -120,6 +121,9 @@ class Library:
         L.dwx_get_tallies.argtypes = [vp, vp, vp]
         L.dwx_rb_enable.argtypes = [vp, i32]
         L.dwx_get_rb_sums.argtypes = [vp, vp, vp]
+        L.dwx_trace_enable.argtypes = [vp, C.c_uint32]
+        L.dwx_trace_info.argtypes = [vp, vp, vp, vp]
+        L.dwx_trace_read.argtypes = [vp, u64, u64, vp, u64, vp]
         L.dwx_get_assignments.argtypes = [vp, i32, vp]
         L.dwx_set_assignments.argtypes = [vp, i32, vp]
         L.dwx_get_sweep.argtypes = [vp, vp]; L.dwx_set_sweep.argtypes = [vp, u64]
@@ -363,6 +367,47 @@ class GibbsSampler:
         assert len(per_row) == len(t) and np.array_equal(np.asarray(base, np.int64), np.cumsum(card) - card)
         with np.errstate(divide="ignore", invalid="ignore"):
             return t.astype(np.float64) / 4294967296.0 / per_row
+
+    # ---- posterior sample trace (no reference counterpart; include/dwx.h) ----
+    def trace_enable(self, capacity):
+        """Keep the inference chain's assignment after each of the last `capacity` inference sweeps, packed, on
+        the device (0: stop recording, keep what is there; another capacity: reallocate, empty)."""
+        self.lib.check(self.lib.L.dwx_trace_enable(self.h, int(capacity)))
+
+    def trace_info(self):
+        """-> (count, capacity, uint64[count] sweep counter of each entry, oldest first)."""
+        cnt, cap = C.c_uint64(0), C.c_uint64(0)
+        self.lib.check(self.lib.L.dwx_trace_info(self.h, C.addressof(cnt), C.addressof(cap), None))
+        ids = np.zeros(cnt.value, np.uint64)
+        if cnt.value:
+            self.lib.check(self.lib.L.dwx_trace_info(self.h, None, None, ids.ctypes.data))
+        return int(cnt.value), int(cap.value), ids
+
+    def trace(self, vids=None, last=None):
+        """-> (uint64[n] sweep ids, uint8[n, len(vids)]): the dense value of every selected variable (reference
+        numbering; default: all owned ones) after each of the last `last` recorded sweeps (default: all held),
+        oldest first -- what assignments("evid") returned right after that sweep."""
+        cnt, _, ids = self.trace_info()
+        n = cnt if last is None else int(last)
+        if vids is not None:
+            vids = np.ascontiguousarray(vids, np.uint64)
+        nv = self.graph.info.num_owned_variables if vids is None else len(vids)
+        out = np.zeros((n, nv), np.uint8)
+        # (a range outside the entries held is the library's error to report)
+        self.lib.check(self.lib.L.dwx_trace_read(self.h, max(cnt - n, 0) if n <= cnt else 0, n,
+                                                 None if vids is None else vids.ctypes.data, nv, out.ctypes.data))
+        return ids[len(ids) - n:] if n <= cnt else ids, out
+
+    def trace_text(self, vids=None, last=None):
+        """inference_result.out.trace.text of `dw gibbs --trace N [--trace_vars FILE]`: "# sweeps: id id ...", then
+        per selected variable "vid <tab> value value ...", oldest sweep first."""
+        ids, t = self.trace(vids, last)
+        if vids is None:
+            vids = range(self.graph.info.num_owned_variables)
+        out = ["# sweeps:" + "".join(" %d" % i for i in ids.tolist()) + "\n"]
+        for col, v in enumerate(vids):
+            out.append("%d\t%s\n" % (int(v), " ".join("%d" % x for x in t[:, col].tolist())) if len(ids) else "%d\n" % int(v))
+        return "".join(out)
 
     def assignments(self, chain):
         out = np.zeros(self.V, np.uint64)

@@ -2497,6 +2497,11 @@ int dwx_get_weights(dwx_sampler *s, double *out) {
 
 int dwx_set_weights(dwx_sampler *s, const double *in) {
   if (!s || !in) return fail(DWX_E_INVALID, "null argument");
+  {
+    std::string why;
+    const int bad = check_sampling_weights(*s->cg, in, &why);
+    if (bad) return fail(bad == 2 ? DWX_E_LIMIT : DWX_E_INVALID, why);
+  }
   return guarded([&]() {
     rt::set_device(s->device);
     const uint32_t W = (uint32_t)s->cg->W;

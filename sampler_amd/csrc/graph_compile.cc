@@ -880,6 +880,24 @@ void compile_graph(const dwx_graph_desc &d, const dwx_compile_opts &o, CompiledG
         });
       }
     }
+    // max |d| over the records that are summed in fixed point (the tiles of dwx_graph_get_fixed_point_mask):
+    // what check_sampling_weights holds every visible weight against
+    g.fix_dmax = 0.0;
+    if (g.edges8.size()) {
+      const size_t nt = g.tiles.size();
+      const uint32_t T = (uint32_t)std::max<size_t>(1, std::min<size_t>(nth, nt));
+      std::vector<float> part(T, 0.0f);
+      parallel_parts(nt, T, [&](uint32_t t, uint64_t tb, uint64_t te) {
+        float m = 0.0f;
+        for (uint64_t ti = tb; ti < te; ++ti) {
+          const TileDesc &td = g.tiles[ti];
+          if (!sorted_eligible(td)) continue;
+          for (uint64_t e = td.e0; e < (uint64_t)td.e0 + td.nedges; ++e) m = std::max(m, std::fabs(sorted_rec_d(g.edges8[e])));
+        }
+        part[t] = m;
+      }, 0);
+      g.fix_dmax = (double)*std::max_element(part.begin(), part.end());
+    }
     // What a multi-GPU driver may assume about the gradient sums (graph_compile.h: grad_shift)
     g.grad_shift = 0; g.grad_unit_max = 0; g.max_records_per_weight = 0;
     if (g.edges8.size() && !g.has_categorical && W > 0 && !o.no_narrow_info) {
@@ -1008,10 +1026,36 @@ void compile_graph(const dwx_graph_desc &d, const dwx_compile_opts &o, CompiledG
     phase("tiles");
     g.w_init.assign(d.w_initial_value, d.w_initial_value + W);
     g.w_fixed.assign(d.w_is_fixed, d.w_is_fixed + W);
+    {
+      std::string why;
+      const int bad = check_sampling_weights(g, g.w_init.data(), &why);
+      if (bad == 2) throw LimitError(why);
+      if (bad) throw std::runtime_error(why);
+    }
   } catch (const LimitError &) {
     *limit = true;
     throw;
   }
+}
+
+// The sampling copy of a weight is its f32 rounding: one that is not finite there makes
+// every potential it enters inf or NaN.  A boolean variable's fixed-point sum clamps each term w32 * d to
+// +-2^19 (pot_fix, factor_functions.h): past the clamp, terms that should cancel no longer do.
+int check_sampling_weights(const CompiledGraph &g, const double *w, std::string *why) {
+  constexpr double kClamp = 524288.0;   // POT_FIX_CLAMP
+  for (uint64_t i = 0; i < g.W; ++i) {
+    // (2^128 - 2^103: the first double that rounds to an infinite f32; NaN fails the comparison)
+    if (!(std::fabs(w[i]) < 3.4028235677973366e38)) {
+      *why = "weight " + std::to_string(i) + " is not finite as the f32 the draws multiply with";
+      return 1;
+    }
+    if (std::fabs((double)(float)w[i]) * g.fix_dmax > kClamp) {
+      *why = "weight " + std::to_string(i) + " times the largest (sign(hit) - sign(miss)) * feature of a fixed-point "
+             "variable exceeds 2^19, the clamp of a term of the fixed-point potential sums";
+      return 2;
+    }
+  }
+  return 0;
 }
 
 // ---------------------------------------------------------------- registry of large host mappings

@@ -67,6 +67,7 @@ struct CompiledGraph {
   // may then all-reduce the gradient sums as 32-bit counts).  grad_shift == 0: not known.
   uint32_t grad_shift = 0;
   uint64_t grad_unit_max = 0, max_records_per_weight = 0;
+  double fix_dmax = 0.0;           // max |d_r| over the records of fixed-point variables (0: there are none)
   std::vector<double> edge_fval64; // [NIdx] or empty
   std::vector<VifRec> vifs;        // [NVif]
   std::vector<uint32_t> tile_v;       // [n_tiles+1]
@@ -87,6 +88,10 @@ struct CompiledGraph {
 
   uint64_t device_bytes() const;
 };
+
+// What the host sees of the weights (compile: the initial ones; dwx_set_weights): 0 = fine, 1 = a weight whose
+// f32 copy is not finite, 2 = |w32| * fix_dmax beyond the clamp of pot_fix; *why says which.
+int check_sampling_weights(const CompiledGraph &g, const double *w, std::string *why);
 
 // A weight-sorted layout: super-tiles + their sorted records (the graph's default one lives in
 // CompiledGraph; a split mini-batch plan builds one per level, cut along its chunks).

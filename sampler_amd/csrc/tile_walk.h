@@ -613,6 +613,16 @@ DWX_DEV void rb_add_owner(const KernelParams &P, uint32_t row, unsigned long lon
 // categorical draw of a small domain goes through the second, linear-space tier -- parity over it)
 constexpr double DRAW_GUARD = DWX_DRAW_GUARD;   // >> every f32 error bound below
 constexpr uint32_t SMALL_CARD = 8;    // domains up to this size are drawn out of registers
+// Where cat_draw's f32 tier may decide: the maximum potential m inside (CAT_FAST_LO, CAT_FAST_HI).  The tier is a
+// true max-subtracted softmax; the reference's sequence is not, in two regimes:
+//   * its logadd chain STARTS at -100000, and that start value holds a share e^(-100000 - m) of the mass.  Above
+//     -99900 the share is < e^-100 (and a cut-off decision it tips moves the sum by < 1e-8, which the guard covers
+//     already); at m <= -100000 it is half of the mass or more;
+//   * its sum lives in log space: every logadd rounds to ulp(|m|) / 2, which shifts every probability by that much,
+//     relatively -- card * 2^-30 below 2^23 (10^-5 for ten thousand values), but all of the mass past 2^52, where
+//     log1p(..) < 1 is absorbed and the first value always wins.
+// Outside the interval the exact sequence decides (so does it for a NaN potential: m stays -1e300).
+constexpr double CAT_FAST_LO = -99900.0, CAT_FAST_HI = 8388608.0;
 
 // a small domain's potentials out of registers (pot[d] for d < card, m their maximum): `times` sweeps' worth
 DWX_DEV void rb_cat_small(const KernelParams &P, uint32_t row0, uint32_t card, const double (&pot)[SMALL_CARD],
@@ -701,7 +711,7 @@ DWX_DEV uint32_t cat_draw(const KernelParams &P, const TileView &T, uint32_t row
         else near = true;
       }
     }
-    if (decided) return pick;
+    if (decided && m > CAT_FAST_LO && m < CAT_FAST_HI) return pick;
 #ifdef DWX_EXP_NOSLOW      // (timing experiment, results invalid: what the exact f64 sequence costs a chunk's critical path)
     return pick;
 #endif
@@ -718,7 +728,8 @@ DWX_DEV uint32_t cat_draw(const KernelParams &P, const TileView &T, uint32_t row
     // taken only 1e-11 L away from both cumulative boundaries and with every cut-off decision 1e-9
     // clear of its threshold -- otherwise (one draw in 10^10) the exact sequence still decides.
     // (|m| < 1000: the reference's sum lives in log space, its rounding error grows with its magnitude
-    // -- 8 ulp(1000) ~ 1e-12 is what the 1e-11 guard covers; larger potentials take the exact path.)
+    // -- 8 ulp(1000) ~ 1e-12 is what the 1e-11 guard covers; larger potentials take the exact path.  Well inside
+    // (CAT_FAST_LO, CAT_FAST_HI): the start value never reaches this tier.)
     if (m > -1000.0 && m < 1000.0) {
       constexpr double CUT = 1.0006809757111146e-08;    // exp(-18.42)
       double e[SMALL_CARD];
@@ -774,20 +785,22 @@ DWX_DEV uint32_t cat_draw(const KernelParams &P, const TileView &T, uint32_t row
       m = v > m ? v : m;
     }
     if (RB) rb_cat_rows(P, row0, card, pot, m);
-    float S = 0.f;
-    for (uint32_t d = 0; d < card; ++d) {
-      const double z = pot[d] - m;
-      S += z > -30.0 ? DWX_FAST_EXPF((float)z) : 0.f;
-    }
-    const double target = r * (double)S, guard = DRAW_GUARD * (double)S;
-    float c = 0.f;
-    for (uint32_t d = 0; d < card; ++d) {
-      const double z = pot[d] - m;
-      const float lo = c;
-      c += z > -30.0 ? DWX_FAST_EXPF((float)z) : 0.f;
-      if ((double)c >= target) {
-        if (target - (double)lo > guard && (double)c - target > guard) return d;
-        break;   // too close to a boundary: let the exact sequence decide
+    if (m > CAT_FAST_LO && m < CAT_FAST_HI) {
+      float S = 0.f;
+      for (uint32_t d = 0; d < card; ++d) {
+        const double z = pot[d] - m;
+        S += z > -30.0 ? DWX_FAST_EXPF((float)z) : 0.f;
+      }
+      const double target = r * (double)S, guard = DRAW_GUARD * (double)S;
+      float c = 0.f;
+      for (uint32_t d = 0; d < card; ++d) {
+        const double z = pot[d] - m;
+        const float lo = c;
+        c += z > -30.0 ? DWX_FAST_EXPF((float)z) : 0.f;
+        if ((double)c >= target) {
+          if (target - (double)lo > guard && (double)c - target > guard) return d;
+          break;   // too close to a boundary: let the exact sequence decide
+        }
       }
     }
     // exact: the reference's sequence on the buffered potentials

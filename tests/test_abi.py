@@ -71,9 +71,15 @@ def test_malformed_graphs_are_rejected():
     with pytest.raises(dwx.DwxError) as e:
         dwx.Graph(raw, lib=lib)
     assert e.value.code == dwx.DWX_E_LIMIT and "65536" in str(e.value)
-    raw = synthetic.cfg2(10, n_weights=2, seed=1)      # fixed weights: no gradient, no limit
+    raw = synthetic.cfg2(10, n_weights=2, seed=1)      # fixed weights: no gradient, no gradient limit
     raw.fac_feature_value[5] = 1e6
+    raw.w_initial_value[:] = [0.25, -0.25]             # (a term 2 w f of 5e5: inside the fixed-point sums' clamp, 2^19)
     dwx.Graph(raw, lib=lib)
+    raw.w_initial_value[:] = [0.25, -0.3]              # 6e5: past it
+    with pytest.raises(dwx.DwxError) as e:
+        dwx.Graph(raw, lib=lib)
+    assert e.value.code == dwx.DWX_E_LIMIT and "2^19" in str(e.value)
+    dwx.Graph(raw, lib=lib, no_compact_records=1)      # (f64 sums: no clamp)
 
 
 def test_empty_graph():

@@ -13,7 +13,6 @@
 #include <cmath>
 #include <cstring>
 #include <map>
-#include <set>
 #include <memory>
 #include <new>
 #include <stdexcept>
@@ -76,6 +75,16 @@ T *upload(const RawArray<T> &v, rt::stream_t s, size_t pad = 0) {
   return d;
 }
 
+// an optional device buffer: nullptr instead of an exception when the device is out of memory (the emulation's
+// runtime layer has the throwing allocator only: host memory)
+void *optional_dmalloc(size_t n) {
+#ifdef DWX_EMU
+  return rt::dmalloc(n);
+#else
+  return rt::try_dmalloc(n);
+#endif
+}
+
 template <class T>
 T *upload_raw(const T *h, size_t n, rt::stream_t s) {
   T *d = (T *)rt::dmalloc(n * sizeof(T));
@@ -90,6 +99,54 @@ struct TimedSpan {
   bool has_pull;
   bool new_sweep;   // the span opens a sweep (inference: always; learning: its first chunk)
   uint32_t n_sweeps = 1;   // ... or several (dwx_sample_n_async on an all-unary graph)
+};
+
+// One build of a sweep-family kernel as this sampler runs it.  dwx_sampler_create resolves every role's build
+// once (resolve_builds) and the launch sites go through launch(): a launch cannot name a build, an LDS size or
+// a grid bound other than the one create set up.
+template <class... A>
+struct Variant {
+  void (*fn)(A...) = nullptr;   // nullptr: the graph never runs this role
+  size_t lds = 0;               // dynamic LDS of every launch
+  unsigned cap = 1;             // workgroups resident on the whole chip: the bound of a persistent grid
+  bool allowed = false;         // the dynamic-LDS allowance of `lds` is set
+  void allow() {
+    if (!allowed) { rt::allow_dynamic_lds(fn, lds); allowed = true; }
+  }
+  // allowance and occupancy at create: the plain builds
+  static Variant eager(void (*f)(A...), size_t bytes) {
+    Variant v;
+    v.fn = f; v.lds = bytes;
+    v.allow();
+    v.cap = rt::resident_blocks(f, BLOCK_THREADS, bytes);
+    return v;
+  }
+  // Another build of this role (RB, TRACE, several sweeps per launch), set up by its first launch, not at
+  // create: a sampler that never runs it pays nothing.  Its persistent grid is the one sized from this build's
+  // occupancy: a build that keeps fewer workgroups resident runs the surplus ones after the first leave --
+  // correct, the tiles are strided.
+  Variant lazy(void (*f)(A...)) const {
+    Variant v = *this;
+    v.fn = f; v.allowed = false;
+    return v;
+  }
+  template <class... B>
+  void launch(unsigned grid, unsigned block, rt::stream_t st, B... args) {
+    if (!fn) throw std::logic_error("a sweep kernel build that dwx_sampler_create did not resolve for this graph");
+    allow();
+    rt::launch(fn, grid, block, lds, st, args...);
+  }
+};
+using SweepVariant = Variant<KernelParams>;
+using SortedVariant = Variant<KernelParams, const SuperTile *, uint32_t, const SortRec8 *, const double *, uint32_t>;
+struct SweepVariants {
+  SweepVariant infer[2];            // the lane tiles' inference sweep, [RB]
+  SweepVariant learn, learn_pull;   // ... learning sweep; the same build staging 16-byte terms only (all_pull)
+  SweepVariant tab[2];              // inference on the 8-byte terms table, [RB]
+  SweepVariant multi[2][2];         // several inference sweeps per launch, [RB][TRACE]
+  Variant<KernelParams, MergeArgs> merged[2];   // a mini-batch with the last one's update as prologue; [1]: a workgroup per tile
+  Variant<KernelParams, PersistArgs> persist;   // a split learning sweep as one launch
+  SortedVariant sorted_infer[2][2], sorted_learn[2];   // weight-sorted super-tiles, [UNI][RB] and [UNI]
 };
 }  // namespace
 
@@ -131,24 +188,18 @@ struct dwx_sampler {
   uint64_t sgd_work_max_launch = 0;           // ... of the colour launch with the most
   bool wide_learn = false;   // the graph has TILE_TERMS2 tiles: 32-byte staged records when learning
   bool tv_pair = false;      // every lane tile is pre-signed unary and / or inline arity-2: sweep_kernel<.., TV_PAIR>
-  unsigned persistent_blocks[2] = {1, 1};
+  SweepVariants kv;                     // the sweep kernels' builds for this graph, resolved at create
   bool rec8 = false;                    // the graph streams 8-byte records (CompiledGraph::edges8)
   bool rp_cat = false;                  // ... with every row pointer of a categorical tile prefetched (K = 6 builds)
-  unsigned persistent_blocks8[2] = {1, 1};
   // every tile that fits is TILE_PULL: a learning sweep with the pull gradient stages 16-byte
   // terms only (no f32 weight array behind the records) -- smaller LDS, one more workgroup per CU
   bool all_pull = false;
-  size_t lds_learn_pull = 0;
-  unsigned persistent_blocks_pull = 1;   // REC8 learning kernel at lds_learn_pull
-  size_t lds_tab = 0;                    // inference on the 8-byte terms table: 8 bytes staged per record
-  unsigned persistent_blocks_tab = 1;
   EdgeRec8 *d_edges8 = nullptr;
   // weight-sorted super-tiles (sorted_sweep_kernel)
   SortRec8 *d_sorted = nullptr;
   SuperTile *d_supers = nullptr;
   double *d_sort_dvals = nullptr;
   uint32_t n_sort_dvals = 0;
-  size_t lds_sorted = 0;
   bool sorted_learn = false;            // ... also in learning sweeps (the super-tiles' tiles pull their gradient)
   bool no_sort_uni = false;             // DWX_NO_SORT_UNI: never the single-d build of sorted_sweep_kernel (A/B)
   bool sorted_fallback_said = false;    // the "more than 8 runs: tile sweep instead" note was printed
@@ -168,7 +219,6 @@ struct dwx_sampler {
   // Rao-Blackwellised marginals (dwx_rb_enable; tile_walk.h rb_*): [R] 32.32 fixed-point sums, device order
   unsigned long long *d_rb = nullptr;   // allocated by the first enable
   bool rb_on = false;                   // inference sweeps run the RB builds of their kernels and accumulate
-  std::set<std::pair<const void *, size_t>> rb_lds_allowed;   // RB / TRACE builds whose dynamic LDS size is already allowed
   // Sample trace (dwx_trace_enable): a ring of the last trace_cap inference sweeps' assignments of
   // the inference chain, packed (aux_kernels.h: trace_pack_kernel), in device order
   unsigned long long *d_trace = nullptr;   // [trace_cap][trace_words], allocated by the first enable
@@ -244,7 +294,6 @@ struct dwx_sampler {
   uint32_t persist_grid = 0, persist_row_stride = 0;
   long long *d_persist_rows = nullptr;
   uint32_t *d_persist_bar = nullptr;
-  size_t lds_persist = 0;
   uint32_t persist_w64_off = 0, persist_red_off = 0;
   bool persist_check_pending = false;
   uint64_t persist_launches = 0;
@@ -254,14 +303,12 @@ struct dwx_sampler {
   long long *d_gbuf[3] = {nullptr, nullptr, nullptr};
   double *d_wbuf64[2] = {nullptr, nullptr};
   float *d_wbuf32[2] = {nullptr, nullptr};
-  size_t lds_merge = 0;
   uint32_t merge_lw32_off = 0;
   uint64_t merged_sweeps = 0;
   int *d_grad32 = nullptr;              // dwx_grad_pack32_async: the gradient sums as 32-bit counts
   uint32_t *d_pack_bad = nullptr;       // ... and its "not a multiple / does not fit" counter
   bool pack_check_pending = false;
   KernelParams base{};
-  size_t lds_bytes[2] = {0, 0};  // [0] inference kernel, [1] learning kernel
   uint64_t sweep = 0;
   uint64_t infer_sweeps = 0;  // inference sweeps since the last clear_tallies
   // kernel timing
@@ -308,23 +355,72 @@ void weights_change(dwx_sampler *s) {
   std::fill(s->pot_valid.begin(), s->pot_valid.end(), (uint8_t)0);
 }
 
-// the dynamic-LDS allowance of an RB build of a sweep kernel: once per sampler, kernel and size
-template <class K>
-void rb_allow_lds(dwx_sampler *s, K kernel, size_t lds) {
-  const std::pair<const void *, size_t> key(reinterpret_cast<const void *>(kernel), lds);
-  if (s->rb_lds_allowed.insert(key).second) rt::allow_dynamic_lds(kernel, lds);
+// no giant, boolean-giant or wide tile: every variable is in a lane tile (the degree bins run kernels of their own)
+bool no_binned_tiles(const dwx_sampler *s) {
+  return s->cgiant_tiles.empty() && s->bgiant_tiles.empty() && s->cg->wide_tiles.empty();
+}
+
+// The sampler's builds of the tile sweep kernels at K records staged per lane and RP row pointers prefetched --
+// the one place that names them; lds_infer / lds_learn: the dynamic LDS of the inference and the learning sweep.
+// Compact-record graphs run sweep8_kernel and its kin, the others sweep_kernel's smallest build that holds their
+// tile classes.  No learning kernel has an RB build.
+template <int K, int RP>
+void make_builds(dwx_sampler *s, size_t lds_infer, size_t lds_learn, size_t lds_tab) {
+  SweepVariants &v = s->kv;
+  if (s->rec8) {
+    v.infer[0] = SweepVariant::eager(sweep8_kernel<false, K, false, RP>, lds_infer);
+    v.infer[1] = v.infer[0].lazy(sweep8_kernel<false, K, false, RP, false, true>);
+    v.multi[0][0] = v.infer[0].lazy(sweep8_kernel<false, K, false, RP, true>);
+    v.multi[1][0] = v.infer[0].lazy(sweep8_kernel<false, K, false, RP, true, true>);
+    v.multi[0][1] = v.infer[0].lazy(sweep8_kernel<false, K, false, RP, true, false, true>);
+    v.multi[1][1] = v.infer[0].lazy(sweep8_kernel<false, K, false, RP, true, true, true>);
+    v.learn = SweepVariant::eager(sweep8_kernel<true, K, false, RP>, lds_learn);
+    // (the smaller size needs no allowance of its own, and setting one would lower the kernel's)
+    v.learn_pull = v.learn;
+    v.learn_pull.lds = lds_tab;
+    v.learn_pull.cap = rt::resident_blocks(v.learn.fn, BLOCK_THREADS, lds_tab);
+    v.tab[0] = SweepVariant::eager(sweep8_kernel<false, K, true, RP>, lds_tab);
+    v.tab[1] = v.tab[0].lazy(sweep8_kernel<false, K, true, RP, false, true>);
+    // (sized and allowed by dwx_sampler_create where the graph qualifies for them)
+    v.merged[0].fn = sweep8_merged_kernel<K, RP>;
+    v.merged[1].fn = sweep8_merged_kernel<K, RP, true>;
+    v.persist.fn = persist_learn8_kernel<K, RP>;
+  } else if (s->tv_pair) {
+    // every tile pre-signed unary and / or inline arity-2 records (config 3b / 5b): the small build (K == 6)
+    v.infer[0] = SweepVariant::eager(sweep_kernel<false, 6, false, TV_PAIR>, lds_infer);
+    v.infer[1] = v.infer[0].lazy(sweep_kernel<false, 6, false, TV_PAIR, true>);
+    v.learn = SweepVariant::eager(sweep_kernel<true, 6, true, TV_PAIR>, lds_learn);
+  } else {
+    v.infer[0] = SweepVariant::eager(sweep_kernel<false, K>, lds_infer);
+    v.infer[1] = v.infer[0].lazy(sweep_kernel<false, K, false, TV_ALL, true>);
+    v.learn = s->wide_learn ? SweepVariant::eager(sweep_kernel<true, K, true>, lds_learn)
+                            : SweepVariant::eager(sweep_kernel<true, K>, lds_learn);
+  }
+}
+void resolve_builds(dwx_sampler *s, size_t lds_infer, size_t lds_learn, size_t lds_tab) {
+  constexpr int RP = (int)ROWPTR_UNROLL;
+  if (s->rp_cat) make_builds<6, (int)ROWPTR_UNROLL_CAT>(s, lds_infer, lds_learn, lds_tab);
+  else switch (s->stage_k) {
+    case 3: make_builds<3, RP>(s, lds_infer, lds_learn, lds_tab); break;
+    case 6: make_builds<6, RP>(s, lds_infer, lds_learn, lds_tab); break;
+    default: make_builds<12, RP>(s, lds_infer, lds_learn, lds_tab); break;
+  }
 }
 
 // launch the sweep kernel (+ the oversized-variable kernel) over tiles [t0, t1) of launch l
 // multi (inference of a graph without degree-binned variables): P.n_sweeps sweeps per launch
 // covered (if given): the end of the gap-free run of weight-sorted super-tiles that starts at t0 (t0: none)
-// RB (inference only): the builds that add every draw's conditional to P.rb (dwx_rb_enable)
-// TRACE (multi only): the builds that write every sweep's draws to the sample trace (dwx_trace_enable)
-template <bool LEARN, bool RB = false, bool TRACE = false>
+// P.rb (inference only): the builds that add every draw's conditional to it (dwx_rb_enable)
+// P.trace (multi only): the builds that write every sweep's draws to the sample trace (dwx_trace_enable)
+template <bool LEARN>
 uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, uint32_t t1, const bool multi = false,
                       uint32_t *covered = nullptr) {
-  static_assert(!(LEARN && RB), "Rao-Blackwellised sums: inference sweeps only");
+  if (LEARN && (P.rb || multi)) throw std::logic_error("Rao-Blackwellised sums, several sweeps per launch: inference sweeps only");
+  const bool rb = P.rb != nullptr, trace = multi && P.trace != nullptr;
+  // (no learning kernel has an RB build: a learning launch names its plain build both times)
+  constexpr bool RBK = !LEARN;
   const CompiledGraph &c = *s->cg;
+  SweepVariants &kv = s->kv;
   if (covered) *covered = t0;
   if (t1 <= t0) return 0;
   uint32_t launches = 0;
@@ -355,69 +451,14 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
   if (b <= a) return;
   P.tile_begin = a;
   P.tile_end = b;
-  const uint32_t t0 = a, t1 = b;
   // persistent grid: as many workgroups as stay resident, each striding over tiles
-  // all-unary graph: 8-byte record stream (a run on the terms table streams those instead)
-  const bool rec8 = s->rec8;
-  const bool tab8 = rec8 && !LEARN && P.edge_terms;   // inference on the 8-byte terms table
-  const bool slim = LEARN && rec8 && s->all_pull && !(P.flags & OPT_NO_PULL);
-  const unsigned grid = std::min<unsigned>(t1 - t0, tab8 ? s->persistent_blocks_tab : slim ? s->persistent_blocks_pull :
-                                           (rec8 ? s->persistent_blocks8 : s->persistent_blocks)[LEARN ? 1 : 0]);
-  // (all-unary graphs stage 8-byte terms whenever the compute phase needs no record)
-  const size_t lds = tab8 ? s->lds_tab : slim ? s->lds_learn_pull : s->lds_bytes[LEARN ? 1 : 0];
-  constexpr int RPC = (int)ROWPTR_UNROLL_CAT;
-  // (the RB builds are set up when they are first launched, not at create: a sampler that never enables pays
-  // nothing.  The persistent grid is the one sized from the plain build's occupancy: a build that keeps fewer
-  // workgroups resident runs the surplus ones after the first leave -- correct, the tiles are strided.)
-  auto go = [&](auto kernel) {
-    if (RB || TRACE) rb_allow_lds(s, kernel, lds);
-    rt::launch(kernel, grid, BLOCK_THREADS, lds, s->stream, P);
-  };
-
-  if constexpr (!LEARN) {
-    if (multi) {   // (only asked for on compact-record graphs, never on the terms table)
-      constexpr int RP = (int)ROWPTR_UNROLL;
-      if (s->rp_cat) go(sweep8_kernel<false, 6, false, RPC, true, RB, TRACE>);
-      else switch (s->stage_k) {
-        case 3: go(sweep8_kernel<false, 3, false, RP, true, RB, TRACE>); break;
-        case 6: go(sweep8_kernel<false, 6, false, RP, true, RB, TRACE>); break;
-        default: go(sweep8_kernel<false, 12, false, RP, true, RB, TRACE>); break;
-      }
-      ++launches;
-      return;
-    }
-  }
-  if (rec8 && s->rp_cat) {
-    if (tab8) go(sweep8_kernel<false, 6, true, RPC, false, RB>);
-    else go(sweep8_kernel<LEARN, 6, false, RPC, false, RB>);
-  } else if (tab8) {
-    switch (s->stage_k) {
-      case 3: go(sweep8_kernel<false, 3, true, (int)ROWPTR_UNROLL, false, RB>); break;
-      case 6: go(sweep8_kernel<false, 6, true, (int)ROWPTR_UNROLL, false, RB>); break;
-      default: go(sweep8_kernel<false, 12, true, (int)ROWPTR_UNROLL, false, RB>); break;
-    }
-  } else if (rec8) {
-    switch (s->stage_k) {
-      case 3: go(sweep8_kernel<LEARN, 3, false, (int)ROWPTR_UNROLL, false, RB>); break;
-      case 6: go(sweep8_kernel<LEARN, 6, false, (int)ROWPTR_UNROLL, false, RB>); break;
-      default: go(sweep8_kernel<LEARN, 12, false, (int)ROWPTR_UNROLL, false, RB>); break;
-    }
-  } else if (s->tv_pair) {
-    // every tile pre-signed unary and / or inline arity-2 records (config 3b / 5b): the small build
-    go(sweep_kernel<LEARN, 6, LEARN, TV_PAIR, RB>);
-  } else if (LEARN && s->wide_learn) {
-    switch (s->stage_k) {
-      case 3: go(sweep_kernel<LEARN, 3, LEARN, TV_ALL, RB>); break;
-      case 6: go(sweep_kernel<LEARN, 6, LEARN, TV_ALL, RB>); break;
-      default: go(sweep_kernel<LEARN, 12, LEARN, TV_ALL, RB>); break;
-    }
-  } else {
-    switch (s->stage_k) {
-      case 3: go(sweep_kernel<LEARN, 3, false, TV_ALL, RB>); break;
-      case 6: go(sweep_kernel<LEARN, 6, false, TV_ALL, RB>); break;
-      default: go(sweep_kernel<LEARN, 12, false, TV_ALL, RB>); break;
-    }
-  }
+  // all-unary graph: 8-byte record stream (a run on the terms table streams those instead;
+  // all-unary graphs stage 8-byte terms whenever the compute phase needs no record)
+  const bool tab8 = s->rec8 && !LEARN && P.edge_terms;   // inference on the 8-byte terms table
+  const bool slim = LEARN && s->rec8 && s->all_pull && !(P.flags & OPT_NO_PULL);
+  // (multi: only asked for on compact-record graphs, never on the terms table)
+  SweepVariant &k = multi ? kv.multi[rb][trace] : tab8 ? kv.tab[rb] : !LEARN ? kv.infer[rb] : slim ? kv.learn_pull : kv.learn;
+  k.launch(std::min<unsigned>(b - a, k.cap), BLOCK_THREADS, s->stream, P);
   ++launches;
   };
   // Weight-sorted super-tiles lying wholly inside [t0, t1): sorted_sweep_kernel, one workgroup
@@ -470,17 +511,10 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
             P.super_rot = n_cached;   // (cached ones lead the run: the range is the launch's first tiles)
         }
         // (one distinct d: the UNI build keeps it in a scalar register; DWX_NO_SORT_UNI: A/B knob)
-        if (s->n_sort_dvals == 2 && !s->no_sort_uni) {
-          if (RB) rb_allow_lds(s, sorted_sweep_kernel<LEARN, true, RB>, s->lds_sorted);
-          rt::launch(sorted_sweep_kernel<LEARN, true, RB>, (unsigned)(r.b - r.a), SORT_THREADS, s->lds_sorted, s->stream, P,
-                     (const SuperTile *)(d_sv + r.a), (uint32_t)(r.b - r.a), d_sr,
-                     (const double *)s->d_sort_dvals, s->n_sort_dvals);
-        } else {
-          if (RB) rb_allow_lds(s, sorted_sweep_kernel<LEARN, false, RB>, s->lds_sorted);
-          rt::launch(sorted_sweep_kernel<LEARN, false, RB>, (unsigned)(r.b - r.a), SORT_THREADS, s->lds_sorted, s->stream, P,
-                     (const SuperTile *)(d_sv + r.a), (uint32_t)(r.b - r.a), d_sr,
-                     (const double *)s->d_sort_dvals, s->n_sort_dvals);
-        }
+        const bool uni = s->n_sort_dvals == 2 && !s->no_sort_uni;
+        (LEARN ? kv.sorted_learn[uni] : kv.sorted_infer[uni][rb])
+            .launch((unsigned)(r.b - r.a), SORT_THREADS, s->stream, P, (const SuperTile *)(d_sv + r.a), (uint32_t)(r.b - r.a), d_sr,
+                    (const double *)s->d_sort_dvals, s->n_sort_dvals);
         ++launches;
         P.super_rot = 0;
         cursor = sv[r.b - 1].tile0 + sv[r.b - 1].ntiles;
@@ -493,7 +527,7 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
   P.tile_end = t1;
   // categorical oversized variables: a workgroup each
   if (cg1 > cg0) {
-    rt::launch(giant_kernel<LEARN, RB>, cg1 - cg0, GIANT_THREADS, 0, st_giant, P,
+    rt::launch(rb ? giant_kernel<LEARN, RBK> : giant_kernel<LEARN>, cg1 - cg0, GIANT_THREADS, 0, st_giant, P,
                (const uint32_t *)(s->d_giant + cg0), cg1 - cg0);
     ++launches;
   }
@@ -502,8 +536,8 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
     const uint32_t p0 = s->bgiant_piece_off[bg0], np = s->bgiant_piece_off[bg1] - p0;
     rt::launch(giant_pot_kernel<LEARN>, np, GIANT_THREADS, 0, st_giant, P, (const uint32_t *)s->d_bgiant,
                (const GiantPiece *)s->d_bgiant_pieces, p0, np, s->d_bgiant_partial);
-    rt::launch(giant_decide_kernel<LEARN, RB>, (bg1 - bg0 + BLOCK_THREADS - 1) / BLOCK_THREADS, BLOCK_THREADS, 0, st_giant, P,
-               (const uint32_t *)s->d_bgiant, (const uint32_t *)s->d_bgiant_piece_off, bg0, bg1 - bg0,
+    rt::launch(rb ? giant_decide_kernel<LEARN, RBK> : giant_decide_kernel<LEARN>, (bg1 - bg0 + BLOCK_THREADS - 1) / BLOCK_THREADS,
+               BLOCK_THREADS, 0, st_giant, P, (const uint32_t *)s->d_bgiant, (const uint32_t *)s->d_bgiant_piece_off, bg0, bg1 - bg0,
                (const double *)s->d_bgiant_partial, s->d_bgiant_decision);
     launches += 2;
     if (LEARN) {
@@ -515,8 +549,8 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
   // mid-degree variables among these tiles: a wave each
   if (w1 > w0) {
     const uint32_t per_block = BLOCK_THREADS / 64u;
-    rt::launch(wide_kernel<LEARN, RB>, (w1 - w0 + per_block - 1) / per_block, BLOCK_THREADS, 0, st_wide, P,
-               (const uint32_t *)(s->d_wide + w0), w1 - w0);
+    rt::launch(rb ? wide_kernel<LEARN, RBK> : wide_kernel<LEARN>, (w1 - w0 + per_block - 1) / per_block, BLOCK_THREADS, 0,
+               st_wide, P, (const uint32_t *)(s->d_wide + w0), w1 - w0);
     ++launches;
   }
   // join: whatever follows on `stream` (the next colour, the pull gradient, an update) waits for all three
@@ -534,8 +568,7 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
 // (sweep8_kernel<..., MULTI>, infer_variable_multi): neither the terms table nor the weight-sorted
 // copy is needed -- a record is read once per n sweeps.
 bool multi_sweep_graph(const dwx_sampler *s) {
-  return s->rec8 && s->cgiant_tiles.empty() && s->bgiant_tiles.empty() && s->cg->wide_tiles.empty() &&
-         !getenv("DWX_NO_MULTI_SWEEP");
+  return s->rec8 && no_binned_tiles(s) && !getenv("DWX_NO_MULTI_SWEEP");
 }
 
 // Sample trace: pack the inference chain's current assignment into n_planes planes of the ring from trace_next on
@@ -561,6 +594,25 @@ void trace_pack(dwx_sampler *s, uint64_t first_id, uint32_t n_planes, bool unsam
   }
 }
 
+// Kernel timing (dwx_options timing): a span's event a goes on the stream where it opens ...
+TimedSpan span_begin(dwx_sampler *s, int kind) {
+  TimedSpan sp{};
+  if (s->timing) {
+    sp.a = rt::event_create(); sp.b = rt::event_create(); sp.c = rt::event_create(); sp.kind = kind;
+    rt::event_record(sp.a, s->stream);
+  }
+  return sp;
+}
+// ... and b and c where it closes (b_recorded: the caller put b between its sweep kernels and its pull gradient)
+void span_end(dwx_sampler *s, TimedSpan &sp, uint32_t launches, bool has_pull, bool new_sweep, uint32_t n_sweeps = 1,
+              bool b_recorded = false) {
+  if (!s->timing) return;
+  if (!b_recorded) rt::event_record(sp.b, s->stream);
+  rt::event_record(sp.c, s->stream);
+  sp.launches = launches; sp.has_pull = has_pull; sp.new_sweep = new_sweep; sp.n_sweeps = n_sweeps;
+  s->spans.push_back(sp);
+}
+
 void enqueue_inference_multi(dwx_sampler *s, uint32_t n) {
   const CompiledGraph &c = *s->cg;
   rt::set_device(s->device);
@@ -569,11 +621,7 @@ void enqueue_inference_multi(dwx_sampler *s, uint32_t n) {
   P.n_sweeps = n;
   P.edge_terms = nullptr;
   P.rb = s->rb_on ? s->d_rb : nullptr;
-  TimedSpan sp{};
-  if (s->timing) {
-    sp.a = rt::event_create(); sp.b = rt::event_create(); sp.c = rt::event_create(); sp.kind = 0;
-    rt::event_record(sp.a, s->stream);
-  }
+  TimedSpan sp = span_begin(s, 0);
   uint32_t launches = 0;
   // the sample trace: the last min(n, capacity) sweeps of the launch write their planes themselves
   // (sweep8_kernel<MULTI, TRACE>), over what trace_pack_kernel leaves there: the unsampled positions' values
@@ -588,17 +636,9 @@ void enqueue_inference_multi(dwx_sampler *s, uint32_t n) {
   for (size_t l = 0; l + 1 < c.launch_off.size(); ++l) {
     const uint32_t t0 = c.launch_tile[l];
     const uint32_t t1 = s->opts.sample_evidence ? c.launch_tile[l + 1] : c.launch_query_tile_end[l];
-    launches += P.trace ? (P.rb ? launch_tiles<false, true, true>(s, P, l, t0, t1, true)
-                                : launch_tiles<false, false, true>(s, P, l, t0, t1, true))
-                        : (P.rb ? launch_tiles<false, true>(s, P, l, t0, t1, true)
-                                : launch_tiles<false>(s, P, l, t0, t1, true));
+    launches += launch_tiles<false>(s, P, l, t0, t1, true);
   }
-  if (s->timing) {
-    rt::event_record(sp.b, s->stream);
-    rt::event_record(sp.c, s->stream);
-    sp.launches = launches; sp.has_pull = false; sp.new_sweep = true; sp.n_sweeps = n;
-    s->spans.push_back(sp);
-  }
+  span_end(s, sp, launches, false, true, n);
   s->sweep += n;
 }
 
@@ -610,11 +650,7 @@ bool pot_cache_ready(dwx_sampler *s) {
     const CompiledGraph &c = *s->cg;
     s->pot_alloc = -1;
     if (s->rec8 && s->d_supers && s->sorted_learn && !getenv("DWX_NO_POT_CACHE")) {
-#ifdef DWX_EMU
-      s->d_pot = (long long *)rt::dmalloc(c.V * sizeof(long long));
-#else
-      s->d_pot = (long long *)rt::try_dmalloc(c.V * sizeof(long long));
-#endif
+      s->d_pot = (long long *)optional_dmalloc(c.V * sizeof(long long));
       if (s->d_pot) {
         s->pot_alloc = 1;
         s->pot_valid.assign(c.launch_tile.size(), 0);
@@ -654,18 +690,13 @@ void enqueue_inference(dwx_sampler *s) {
   // the potential cache is stored once a learning sweep is known to follow inference sweeps (on a
   // sampler that only infers, it would be bandwidth spent for nothing -- the rule of the terms table)
   P.pot = (s->pot_wanted && !P.edge_terms && pot_cache_ready(s)) ? s->d_pot : nullptr;
-  TimedSpan sp{};
-  if (s->timing) {
-    sp.a = rt::event_create(); sp.b = rt::event_create(); sp.c = rt::event_create(); sp.kind = 0;
-    rt::event_record(sp.a, s->stream);
-  }
+  TimedSpan sp = span_begin(s, 0);
   uint32_t launches = 0;
   for (size_t l = 0; l + 1 < c.launch_off.size(); ++l) {
     // only the query variables' tiles unless --sample_evidence (src/gibbs_sampler.h:157)
     const uint32_t t1 = s->opts.sample_evidence ? c.launch_tile[l + 1] : c.launch_query_tile_end[l];
     uint32_t covered = 0;
-    launches += P.rb ? launch_tiles<false, true>(s, P, l, c.launch_tile[l], t1, false, &covered)
-                     : launch_tiles<false>(s, P, l, c.launch_tile[l], t1, false, &covered);
+    launches += launch_tiles<false>(s, P, l, c.launch_tile[l], t1, false, &covered);
     // valid for launch l only if sorted_sweep_kernel stored the sum of EVERY query tile (none took the
     // tile sweep, the terms table or a degree-bin kernel)
     if (P.pot && c.launch_query_tile_end[l] > c.launch_tile[l] && covered >= c.launch_query_tile_end[l]) s->pot_valid[l] = 1;
@@ -675,12 +706,7 @@ void enqueue_inference(dwx_sampler *s) {
     trace_pack(s, s->sweep, 1, false);
     ++launches;
   }
-  if (s->timing) {
-    rt::event_record(sp.b, s->stream);
-    rt::event_record(sp.c, s->stream);
-    sp.launches = launches; sp.has_pull = false; sp.new_sweep = true;
-    s->spans.push_back(sp);
-  }
+  span_end(s, sp, launches, false, true);
   ++s->sweep;
 }
 
@@ -1508,14 +1534,9 @@ void enqueue_learn_chunk(dwx_sampler *s, uint32_t chunk) {
     P.pot_v1 = c.tile_v[c.launch_query_tile_end[l]];
     if (chunk == 0) ++s->pot_sweeps;
   }
-  TimedSpan sp{};
-  const bool timing = s->timing;
-  if (timing) {
-    sp.a = rt::event_create(); sp.b = rt::event_create(); sp.c = rt::event_create(); sp.kind = 1;
-    rt::event_record(sp.a, s->stream);
-  }
+  TimedSpan sp = span_begin(s, 1);
   const uint32_t launches = launch_tiles<true>(s, P, ch.launch, ch.t0, ch.t1);
-  if (timing) rt::event_record(sp.b, s->stream);
+  if (s->timing) rt::event_record(sp.b, s->stream);
   bool pulled = false;
   // the pull-based gradient of the TILE_PULL tiles: un-split sweeps once, after the last
   // chunk (= colour launch), over the whole list; split sweeps per chunk over its part
@@ -1569,11 +1590,7 @@ void enqueue_learn_chunk(dwx_sampler *s, uint32_t chunk) {
     pulled = true;
   }
   if (pe > pb) launch_list(s->stream);
-  if (timing) {
-    rt::event_record(sp.c, s->stream);
-    sp.launches = launches; sp.has_pull = pulled; sp.new_sweep = chunk == 0;
-    s->spans.push_back(sp);
-  }
+  span_end(s, sp, launches, pulled, chunk == 0, 1, true);
 }
 
 void enqueue_apply(dwx_sampler *s) {
@@ -1623,7 +1640,7 @@ bool enqueue_merged_sweep(dwx_sampler *s) {
   }
   s->d_gbuf[0] = s->d_grad;
   if (s->plan_level) ++s->plan_level->sweeps;
-  const unsigned cap = s->persistent_blocks8[1];
+  const unsigned cap = s->kv.learn.cap;
   // The leading tiles of the first mini-batch in which NOTHING learns -- the query part of the colour launch:
   // half of config 4's tiles, 190 us of bandwidth work at the head of 63 latency-bound launches of 16 us -- run
   // beside the mini-batches instead of ahead of them: on a side stream, one workgroup per CU (the mini-batches'
@@ -1646,13 +1663,7 @@ bool enqueue_merged_sweep(dwx_sampler *s) {
     unsigned side_wgs = std::max(1u, rt::grid_barrier_blocks());
     if (const char *e = getenv("DWX_QUIET_GRID")) side_wgs = (unsigned)std::max(1L, atol(e));   // (tuning knob)
     const unsigned grid = std::min<unsigned>(quiet_end - Q.tile_begin, side_wgs);
-    const size_t lds = s->lds_bytes[1];
-    if (s->rp_cat) rt::launch(sweep8_kernel<true, 6, false, (int)ROWPTR_UNROLL_CAT>, grid, BLOCK_THREADS, lds, s->side[0], Q);
-    else switch (s->stage_k) {
-      case 3: rt::launch(sweep8_kernel<true, 3>, grid, BLOCK_THREADS, lds, s->side[0], Q); break;
-      case 6: rt::launch(sweep8_kernel<true, 6>, grid, BLOCK_THREADS, lds, s->side[0], Q); break;
-      default: rt::launch(sweep8_kernel<true, 12>, grid, BLOCK_THREADS, lds, s->side[0], Q); break;
-    }
+    s->kv.learn.launch(grid, BLOCK_THREADS, s->side[0], Q);
     rt::event_record(s->ev_join[0], s->side[0]);
   }
   for (uint32_t ci = 0; ci < n; ++ci) {
@@ -1674,44 +1685,18 @@ bool enqueue_merged_sweep(dwx_sampler *s) {
     M.stepsize = s->plan_eta; M.reg_param = s->opts.reg_param;
     M.l2 = s->opts.regularization == 1 ? 1 : 0;
     M.lds_lw32_off = s->merge_lw32_off;
-    TimedSpan sp{};
-    if (s->timing) {
-      sp.a = rt::event_create(); sp.b = rt::event_create(); sp.c = rt::event_create(); sp.kind = 1;
-      rt::event_record(sp.a, s->stream);
-    }
+    TimedSpan sp = span_begin(s, 1);
     if (ch.t1 > ch.t0 && ch.t1 - ch.t0 <= cap && !getenv("DWX_NO_ONE_TILE")) {
       // a workgroup per tile (the usual shape of a mini-batch): the build without the next-tile machinery
-      const unsigned grid = ch.t1 - ch.t0;
-      if (s->rp_cat) rt::launch(sweep8_merged_kernel<6, (int)ROWPTR_UNROLL_CAT, true>, grid, BLOCK_THREADS, s->lds_merge, s->stream, P, M);
-      else switch (s->stage_k) {
-        case 3: rt::launch(sweep8_merged_kernel<3, (int)ROWPTR_UNROLL, true>, grid, BLOCK_THREADS, s->lds_merge, s->stream, P, M); break;
-        case 6: rt::launch(sweep8_merged_kernel<6, (int)ROWPTR_UNROLL, true>, grid, BLOCK_THREADS, s->lds_merge, s->stream, P, M); break;
-        default: rt::launch(sweep8_merged_kernel<12, (int)ROWPTR_UNROLL, true>, grid, BLOCK_THREADS, s->lds_merge, s->stream, P, M); break;
-      }
+      s->kv.merged[1].launch(ch.t1 - ch.t0, BLOCK_THREADS, s->stream, P, M);
     } else if (ch.t1 > ch.t0) {
-      const unsigned grid = std::min<unsigned>(ch.t1 - ch.t0, cap);
-      if (s->rp_cat) rt::launch(sweep8_merged_kernel<6, (int)ROWPTR_UNROLL_CAT>, grid, BLOCK_THREADS, s->lds_merge, s->stream, P, M);
-      else switch (s->stage_k) {
-        case 3: rt::launch(sweep8_merged_kernel<3, (int)ROWPTR_UNROLL>, grid, BLOCK_THREADS, s->lds_merge, s->stream, P, M); break;
-        case 6: rt::launch(sweep8_merged_kernel<6, (int)ROWPTR_UNROLL>, grid, BLOCK_THREADS, s->lds_merge, s->stream, P, M); break;
-        default: rt::launch(sweep8_merged_kernel<12, (int)ROWPTR_UNROLL>, grid, BLOCK_THREADS, s->lds_merge, s->stream, P, M); break;
-      }
+      s->kv.merged[0].launch(std::min<unsigned>(ch.t1 - ch.t0, cap), BLOCK_THREADS, s->stream, P, M);
     } else {
       // (an empty chunk: the update alone, through a one-workgroup launch over no tile)
       P.tile_begin = P.tile_end = 0;
-      if (s->rp_cat) rt::launch(sweep8_merged_kernel<6, (int)ROWPTR_UNROLL_CAT>, 1u, BLOCK_THREADS, s->lds_merge, s->stream, P, M);
-      else switch (s->stage_k) {
-        case 3: rt::launch(sweep8_merged_kernel<3, (int)ROWPTR_UNROLL>, 1u, BLOCK_THREADS, s->lds_merge, s->stream, P, M); break;
-        case 6: rt::launch(sweep8_merged_kernel<6, (int)ROWPTR_UNROLL>, 1u, BLOCK_THREADS, s->lds_merge, s->stream, P, M); break;
-        default: rt::launch(sweep8_merged_kernel<12, (int)ROWPTR_UNROLL>, 1u, BLOCK_THREADS, s->lds_merge, s->stream, P, M); break;
-      }
+      s->kv.merged[0].launch(1u, BLOCK_THREADS, s->stream, P, M);
     }
-    if (s->timing) {
-      rt::event_record(sp.b, s->stream);
-      rt::event_record(sp.c, s->stream);
-      sp.launches = 1; sp.has_pull = false; sp.new_sweep = ci == 0;
-      s->spans.push_back(sp);
-    }
+    span_end(s, sp, 1, false, ci == 0);
   }
   // the last mini-batch's update: from the weights the last merged launch wrote, into the sampler's own arrays
   if (aside) rt::stream_wait_event(s->stream, s->ev_join[0]);   // (the quiet tiles still read those arrays)
@@ -1764,24 +1749,10 @@ bool enqueue_persistent_sweep(dwx_sampler *s) {
   A.l2 = s->opts.regularization == 1 ? 1 : 0;
   A.spin_limit = 4u << 20;
   A.lds_w64_off = s->persist_w64_off; A.lds_red_off = s->persist_red_off;
-  TimedSpan sp{};
-  if (s->timing) {
-    sp.a = rt::event_create(); sp.b = rt::event_create(); sp.c = rt::event_create(); sp.kind = 1;
-    rt::event_record(sp.a, s->stream);
-  }
+  TimedSpan sp = span_begin(s, 1);
   rt::dmemset(s->d_persist_bar, 0, 16, s->stream);
-  if (s->rp_cat) rt::launch(persist_learn8_kernel<6, (int)ROWPTR_UNROLL_CAT>, A.grid, BLOCK_THREADS, s->lds_persist, s->stream, P, A);
-  else switch (s->stage_k) {
-    case 3: rt::launch(persist_learn8_kernel<3, (int)ROWPTR_UNROLL>, A.grid, BLOCK_THREADS, s->lds_persist, s->stream, P, A); break;
-    case 6: rt::launch(persist_learn8_kernel<6, (int)ROWPTR_UNROLL>, A.grid, BLOCK_THREADS, s->lds_persist, s->stream, P, A); break;
-    default: rt::launch(persist_learn8_kernel<12, (int)ROWPTR_UNROLL>, A.grid, BLOCK_THREADS, s->lds_persist, s->stream, P, A); break;
-  }
-  if (s->timing) {
-    rt::event_record(sp.b, s->stream);
-    rt::event_record(sp.c, s->stream);
-    sp.launches = 1; sp.has_pull = false; sp.new_sweep = true;
-    s->spans.push_back(sp);
-  }
+  s->kv.persist.launch(A.grid, BLOCK_THREADS, s->stream, P, A);
+  span_end(s, sp, 1, false, true);
   weights_change(s);
   s->cur_chunk = n - 1;
   s->persist_check_pending = true;
@@ -1992,12 +1963,16 @@ int dwx_sampler_create(const dwx_graph *g, const dwx_options *opts, dwx_sampler 
       }
       s->d_sort_dvals = upload(c.sort_dvals, st);
       s->n_sort_dvals = (uint32_t)c.sort_dvals.size();
-      s->lds_sorted = (size_t)SUPER_NV_MAX * 8 + SORT_TV_SLOTS * 4 + (size_t)s->n_sort_dvals * 8;
       s->sorted_learn = c.W > LDS_AGG_MAX_W;     // == their tiles are TILE_PULL
-      rt::allow_dynamic_lds(sorted_sweep_kernel<false, false>, s->lds_sorted);
-      rt::allow_dynamic_lds(sorted_sweep_kernel<true, false>, s->lds_sorted);
-      rt::allow_dynamic_lds(sorted_sweep_kernel<false, true>, s->lds_sorted);
-      rt::allow_dynamic_lds(sorted_sweep_kernel<true, true>, s->lds_sorted);
+      // [UNI: one distinct d]; the RB builds are allowed by their first launch
+      const size_t lds_sorted = (size_t)SUPER_NV_MAX * 8 + SORT_TV_SLOTS * 4 + (size_t)s->n_sort_dvals * 8;
+      auto set = [&](SortedVariant &k, auto fn, bool rb) { k.fn = fn; k.lds = lds_sorted; if (!rb) k.allow(); };
+      set(s->kv.sorted_infer[0][0], sorted_sweep_kernel<false, false>, false);
+      set(s->kv.sorted_infer[0][1], sorted_sweep_kernel<false, false, true>, true);
+      set(s->kv.sorted_infer[1][0], sorted_sweep_kernel<false, true>, false);
+      set(s->kv.sorted_infer[1][1], sorted_sweep_kernel<false, true, true>, true);
+      set(s->kv.sorted_learn[0], sorted_sweep_kernel<true, false>, false);
+      set(s->kv.sorted_learn[1], sorted_sweep_kernel<true, true>, false);
       s->no_sort_uni = getenv("DWX_NO_SORT_UNI") != nullptr;
       s->pot_query_first = getenv("DWX_POT_QUERY_FIRST") != nullptr;
     }
@@ -2059,7 +2034,7 @@ int dwx_sampler_create(const dwx_graph *g, const dwx_options *opts, dwx_sampler 
     s->wide_learn = c.n_terms2_tiles > 0 && s->stage_k <= 6;
     off += slots * sizeof(EdgeRec);
     P.lds_w_off = (uint32_t)off;     // f32 weights right behind the 16-byte records
-    s->lds_bytes[0] = off;
+    const size_t lds_infer = off;
     {
       // the tile classes this graph holds: sweep_kernel's smallest build that contains them
       uint32_t tv = 0;
@@ -2077,101 +2052,42 @@ int dwx_sampler_create(const dwx_graph *g, const dwx_options *opts, dwx_sampler 
     }
     // learning: 16-byte records + f32 weights (20 B per slot); with TILE_TERMS2 tiles the same region
     // alternatively holds 32-byte LearnRecs (which carry their weight) -- 16-byte ones in the TV_PAIR build
-    s->lds_bytes[1] = P.lds_edge_off + slots * (s->wide_learn && !s->tv_pair ? 32 : 20);
+    size_t lds_learn = P.lds_edge_off + slots * (s->wide_learn && !s->tv_pair ? 32 : 20);
     P.lds_agg_off = 0;
     P.n_sweeps = 1;
     if (c.W > 0 && c.W <= LDS_AGG_MAX_W) {
-      P.lds_agg_off = (uint32_t)((s->lds_bytes[1] + 15) & ~(size_t)15);
-      s->lds_bytes[1] = P.lds_agg_off + (size_t)c.W * 16;
+      P.lds_agg_off = (uint32_t)((lds_learn + 15) & ~(size_t)15);
+      lds_learn = P.lds_agg_off + (size_t)c.W * 16;
     }
-    if (s->lds_bytes[1] > 160 * 1024) throw std::invalid_argument("tile does not fit the 160 KiB LDS");
-    auto prepare = [&](auto infer, auto learn) {
-      rt::allow_dynamic_lds(infer, s->lds_bytes[0]);
-      rt::allow_dynamic_lds(learn, s->lds_bytes[1]);
-      s->persistent_blocks[0] = rt::resident_blocks(infer, BLOCK_THREADS, s->lds_bytes[0]);
-      s->persistent_blocks[1] = rt::resident_blocks(learn, BLOCK_THREADS, s->lds_bytes[1]);
-    };
-    if (s->tv_pair) {
-      prepare(sweep_kernel<false, 6, false, TV_PAIR>, sweep_kernel<true, 6, true, TV_PAIR>);
-    } else if (s->wide_learn) {
-      switch (s->stage_k) {
-        case 3: prepare(sweep_kernel<false, 3>, sweep_kernel<true, 3, true>); break;
-        case 6: prepare(sweep_kernel<false, 6>, sweep_kernel<true, 6, true>); break;
-        default: prepare(sweep_kernel<false, 12>, sweep_kernel<true, 12, true>); break;
-      }
-    } else {
-      switch (s->stage_k) {
-        case 3: prepare(sweep_kernel<false, 3>, sweep_kernel<true, 3>); break;
-        case 6: prepare(sweep_kernel<false, 6>, sweep_kernel<true, 6>); break;
-        default: prepare(sweep_kernel<false, 12>, sweep_kernel<true, 12>); break;
-      }
-    }
+    if (lds_learn > 160 * 1024) throw std::invalid_argument("tile does not fit the 160 KiB LDS");
     if (s->rec8) {
       s->all_pull = P.lds_agg_off == 0;   // (TILE_PULL implies it; a graph of oversized variables only has no such tile)
       for (const TileDesc &td : c.tiles)
         if (!(td.flags & TILE_OUTSIDE) && !(td.flags & TILE_PULL)) { s->all_pull = false; break; }
-      s->lds_tab = P.lds_edge_off + (size_t)s->stage_k * BLOCK_THREADS * 8;
-      s->lds_learn_pull = s->lds_tab;
-      auto prepare8 = [&](auto infer, auto learn) {
-        rt::allow_dynamic_lds(infer, s->lds_bytes[0]);
-        rt::allow_dynamic_lds(learn, s->lds_bytes[1]);
-        s->persistent_blocks8[0] = rt::resident_blocks(infer, BLOCK_THREADS, s->lds_bytes[0]);
-        s->persistent_blocks8[1] = rt::resident_blocks(learn, BLOCK_THREADS, s->lds_bytes[1]);
-        s->persistent_blocks_pull = rt::resident_blocks(learn, BLOCK_THREADS, s->lds_learn_pull);
-      };
-      auto prepare_tab = [&](auto tab) {
-        rt::allow_dynamic_lds(tab, s->lds_tab);
-        s->persistent_blocks_tab = rt::resident_blocks(tab, BLOCK_THREADS, s->lds_tab);
-      };
-      if (s->rp_cat) {
-        constexpr int RPC = (int)ROWPTR_UNROLL_CAT;
-        prepare8(sweep8_kernel<false, 6, false, RPC>, sweep8_kernel<true, 6, false, RPC>);
-        prepare_tab(sweep8_kernel<false, 6, true, RPC>);
-      } else
-      switch (s->stage_k) {
-        case 3: prepare8(sweep8_kernel<false, 3>, sweep8_kernel<true, 3>); prepare_tab(sweep8_kernel<false, 3, true>); break;
-        case 6: prepare8(sweep8_kernel<false, 6>, sweep8_kernel<true, 6>); prepare_tab(sweep8_kernel<false, 6, true>); break;
-        default: prepare8(sweep8_kernel<false, 12>, sweep8_kernel<true, 12>); prepare_tab(sweep8_kernel<false, 12, true>); break;
-      }
     }
-    if (P.lds_agg_off && s->rec8 && s->cgiant_tiles.empty() && s->bgiant_tiles.empty() && c.wide_tiles.empty() &&
-        !getenv("DWX_NO_MERGED_APPLY")) {
+    // (inference on the 8-byte terms table, learning with the pull gradient alone: 8 bytes staged per record)
+    resolve_builds(s.get(), lds_infer, lds_learn, P.lds_edge_off + slots * 8);
+    if (P.lds_agg_off && s->rec8 && no_binned_tiles(s.get()) && !getenv("DWX_NO_MERGED_APPLY")) {
       // split learning sweeps, one launch per mini-batch: the update as the next sweep kernel's prologue
-      s->merge_lw32_off = (uint32_t)((s->lds_bytes[1] + 15) & ~(size_t)15);
-      s->lds_merge = s->merge_lw32_off + (size_t)c.W * 4 + 16;
-      s->merge_ok = s->lds_merge <= 160 * 1024;
-      if (s->merge_ok) {
-        if (s->rp_cat) {
-          rt::allow_dynamic_lds(sweep8_merged_kernel<6, (int)ROWPTR_UNROLL_CAT>, s->lds_merge);
-          rt::allow_dynamic_lds(sweep8_merged_kernel<6, (int)ROWPTR_UNROLL_CAT, true>, s->lds_merge);
-        } else switch (s->stage_k) {
-          case 3: rt::allow_dynamic_lds(sweep8_merged_kernel<3, (int)ROWPTR_UNROLL>, s->lds_merge);
-                  rt::allow_dynamic_lds(sweep8_merged_kernel<3, (int)ROWPTR_UNROLL, true>, s->lds_merge); break;
-          case 6: rt::allow_dynamic_lds(sweep8_merged_kernel<6, (int)ROWPTR_UNROLL>, s->lds_merge);
-                  rt::allow_dynamic_lds(sweep8_merged_kernel<6, (int)ROWPTR_UNROLL, true>, s->lds_merge); break;
-          default: rt::allow_dynamic_lds(sweep8_merged_kernel<12, (int)ROWPTR_UNROLL>, s->lds_merge);
-                   rt::allow_dynamic_lds(sweep8_merged_kernel<12, (int)ROWPTR_UNROLL, true>, s->lds_merge); break;
-        }
-      }
+      s->merge_lw32_off = (uint32_t)((lds_learn + 15) & ~(size_t)15);
+      const size_t lds_merge = s->merge_lw32_off + (size_t)c.W * 4 + 16;
+      s->merge_ok = lds_merge <= 160 * 1024;
+      if (s->merge_ok)
+        for (auto &k : s->kv.merged) { k.lds = lds_merge; k.allow(); }
     }
-    if (P.lds_agg_off && c.W <= PERSIST_MAX_W && s->rec8 && s->cgiant_tiles.empty() && s->bgiant_tiles.empty() &&
-        c.wide_tiles.empty() && getenv("DWX_PERSIST") && !getenv("DWX_NO_PERSIST")) {
+    if (P.lds_agg_off && c.W <= PERSIST_MAX_W && s->rec8 && no_binned_tiles(s.get()) && getenv("DWX_PERSIST") &&
+        !getenv("DWX_NO_PERSIST")) {
       // a split learning sweep as one persistent launch (opt-in): at most one workgroup per CU, all resident
       s->persist_grid = rt::grid_barrier_blocks();
       if (const char *e = getenv("DWX_PERSIST_WG_PER_CU")) s->persist_grid *= (uint32_t)std::max(1L, std::min(3L, atol(e)));   // (experiment)
       s->persist_row_stride = (uint32_t)((2 * c.W + 15) / 16 * 16);
       s->d_persist_rows = (long long *)rt::dmalloc((size_t)2 * s->persist_grid * s->persist_row_stride * 8);
       s->d_persist_bar = (uint32_t *)rt::dmalloc(16);
-      s->persist_w64_off = (uint32_t)((s->lds_bytes[1] + 15) & ~(size_t)15);
+      s->persist_w64_off = (uint32_t)((lds_learn + 15) & ~(size_t)15);
       s->persist_red_off = (uint32_t)((s->persist_w64_off + c.W * 12 + 15) & ~(size_t)15);
-      s->lds_persist = s->persist_red_off + (size_t)BLOCK_THREADS * 8 + 16;
-      if (s->lds_persist > 160 * 1024) s->persist_grid = 0;
-      else if (s->rp_cat) rt::allow_dynamic_lds(persist_learn8_kernel<6, (int)ROWPTR_UNROLL_CAT>, s->lds_persist);
-      else switch (s->stage_k) {
-        case 3: rt::allow_dynamic_lds(persist_learn8_kernel<3, (int)ROWPTR_UNROLL>, s->lds_persist); break;
-        case 6: rt::allow_dynamic_lds(persist_learn8_kernel<6, (int)ROWPTR_UNROLL>, s->lds_persist); break;
-        default: rt::allow_dynamic_lds(persist_learn8_kernel<12, (int)ROWPTR_UNROLL>, s->lds_persist); break;
-      }
+      s->kv.persist.lds = s->persist_red_off + (size_t)BLOCK_THREADS * 8 + 16;
+      if (s->kv.persist.lds > 160 * 1024) s->persist_grid = 0;
+      else s->kv.persist.allow();
     }
     rt::stream_sync(st);
     // the un-split sweep's curvature estimate is needed by the first dwx_sgd_plan: pay
@@ -2185,10 +2101,7 @@ int dwx_sampler_create(const dwx_graph *g, const dwx_options *opts, dwx_sampler 
           const TileDesc &td = c.tiles[ti];
           uint64_t n = 0;
           for (uint32_t p = td.v0; p < td.v0 + td.nv; ++p) {
-            const uint32_t m = c.v_meta[p];
-            const bool trig = opts->learn_non_evidence || (!opts->noise_aware && (m & VM_EVIDENCE)) ||
-                              (opts->noise_aware && (m & VM_TRUTHINESS));
-            if (!trig) continue;
+            if (!triggers_sgd(*opts, c.v_meta[p])) continue;
             for (uint32_t e = c.row_ptr[c.v_row[p]]; e < c.row_ptr[c.v_row[p + 1]]; ++e)
               n += !(c.edges[e].packed & EDGE_FIXED_FLAG);
           }
@@ -2552,11 +2465,7 @@ int dwx_rb_enable(dwx_sampler *s, int on) {
     int rc = guarded([&]() {
       rt::set_device(s->device);
       const size_t bytes = ((size_t)s->cg->R + 1) * 8;
-#ifdef DWX_EMU
-      void *p = rt::dmalloc(bytes);
-#else
-      void *p = rt::try_dmalloc(bytes);
-#endif
+      void *p = optional_dmalloc(bytes);
       if (!p) return;
       rt::dmemset(p, 0, bytes, s->stream);
       s->d_rb = (unsigned long long *)p;
@@ -2607,11 +2516,7 @@ int dwx_trace_enable(dwx_sampler *s, uint32_t capacity_sweeps) {
       rt::stream_sync(s->stream);   // (a sweep in flight may still write the ring about to be freed)
       rt::dfree(s->d_trace);
       s->d_trace = nullptr; s->trace_on = false; s->trace_cap = s->trace_next = s->trace_count = 0;
-#ifdef DWX_EMU
-      p = rt::dmalloc(bytes);
-#else
-      p = rt::try_dmalloc(bytes);
-#endif
+      p = optional_dmalloc(bytes);
       if (p) rt::dmemset(p, 0, bytes, s->stream);
     });
     if (rc != DWX_OK) return rc;

@@ -49,7 +49,8 @@ inline void (*&oom_hook())(int) {
   static void (*hook)(int) = nullptr;
   return hook;
 }
-inline void *dmalloc(size_t n) {
+// (an optional buffer: nullptr instead of an exception when the device is out of memory, the hook tried)
+inline void *try_dmalloc(size_t n, hipError_t *why = nullptr) {
   void *p = nullptr;
   hipError_t e = hipMalloc(&p, n ? n : 16);
   if (e != hipSuccess && oom_hook()) {
@@ -58,20 +59,14 @@ inline void *dmalloc(size_t n) {
     if (hipGetDevice(&dev) == hipSuccess) oom_hook()(dev);
     e = hipMalloc(&p, n ? n : 16);
   }
-  DWX_HIP(e);
+  if (why) *why = e;
+  if (e != hipSuccess) { (void)hipGetLastError(); return nullptr; }
   return p;
 }
-// (an optional buffer: nullptr instead of an exception when the device is out of memory, the hook tried)
-inline void *try_dmalloc(size_t n) {
-  void *p = nullptr;
-  hipError_t e = hipMalloc(&p, n ? n : 16);
-  if (e != hipSuccess && oom_hook()) {
-    (void)hipGetLastError();
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) oom_hook()(dev);
-    e = hipMalloc(&p, n ? n : 16);
-  }
-  if (e != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+inline void *dmalloc(size_t n) {
+  hipError_t e = hipSuccess;
+  void *p = try_dmalloc(n, &e);
+  check(e, "hipMalloc");
   return p;
 }
 inline void dfree(void *p) { if (p) (void)hipFree(p); }

@@ -364,6 +364,49 @@ int dwx_trace_enable(dwx_sampler *s, uint32_t capacity_sweeps);
 int dwx_trace_info(dwx_sampler *s, uint64_t *count, uint64_t *capacity, uint64_t *sweep_ids);
 int dwx_trace_read(dwx_sampler *s, uint64_t first_entry, uint64_t n_entries, const uint64_t *vids, uint64_t n_vids,
                    uint8_t *out);
+/* Split-R-hat and effective sample size of EVERY value row, computed on the device from the ring where it lies.
+ * NO reference counterpart: the reference only counts the drawn values (sample_single_variable,
+ * src/gibbs_sampler.h:160-167) and keeps no sequence to judge.  dwx_trace_read + sampler_amd/diagnostics.py is
+ * the route for a selection of variables and for several chains; this one reads the ring once (n x ceil(V / 64)
+ * x 8 bytes at a bit per variable) and returns two doubles per row, or the summary alone.
+ * Rows are value rows in the REFERENCE numbering, as in dwx_get_tallies and dwx_graph_get_values: a boolean
+ * variable has one row, the indicator of value 1; a categorical variable one row per dense value d, the indicator
+ * x == d.  Every owned variable gets its rows, sampled or not (an unsampled variable's series is whatever the
+ * trace holds for it); ghost variables have none, their rows of the arrays are left as they were.
+ * Definition (single chain).  x_0 .. x_{n-1}: a row's 0/1 series over the n entries held, oldest first; the
+ * entries are taken as consecutive whatever their sweep ids (summary.contiguous tells).  Integer statistics:
+ *   k = sum x_i;  h = n / 2 (integer);  k1 = sum_{i < h} x_i;  k2 = sum_{i >= n - h} x_i (the middle draw of an
+ *   odd n is dropped);  for t = 0 .. max_lag:  c_t = sum_{i < n - t} x_i x_{i+t},  H_t = sum_{i < n - t} x_i,
+ *   T_t = sum_{i >= t} x_i.
+ * split-R-hat, in f64 as IEEE arithmetic has it:
+ *   var_j = (k_j - k_j^2 / h) / (h - 1);  W_s = (var_1 + var_2) / 2;  B = (k1 / h - k2 / h)^2 / 2;
+ *   rhat = sqrt(((h - 1) / h * W_s + B) / W_s):  nan when W_s = 0 and B = 0, +inf when W_s = 0 and B > 0 (halves
+ *   that are constant and different) -- diagnostics.split_rhat of the same draws.
+ * ESS: nan when k = 0 or k = n.  Otherwise m = k / n, W = (k - k^2 / n) / (n - 1), var+ = (k - k^2 / n) / n,
+ *   a_t = (c_t - m (H_t + T_t) + (n - t) m^2) / n,  rho_t = 1 - (W - a_t) / var+,  and Geyer's initial positive
+ *   sequence: t = 0, s = 0; while t + 1 < n: pair = rho_t + rho_{t+1}; stop if !(pair > 0); s += pair; t += 2.
+ *   tau = 1 + 2 (s - rho_0) if t > 0 else 1;  ess = n / tau -- diagnostics.ess of that one chain.  Where the loop
+ *   would need rho_{t+1} with t + 1 > max_lag it stops there instead: the row is flagged truncated and its ess,
+ *   from the pairs summed so far, is an upper bound.
+ * rhat, ess ([num_values] doubles) and flags ([num_values] bytes: bit 0 constant, bit 1 truncated) may each be
+ * null; with all three null only the summary crosses to the host.  summary may be null, but not with all three.
+ * DWX_E_INVALID: trace never enabled, fewer than 4 entries held, max_lag outside 1 .. 64, nothing to return.
+ * DWX_E_NOMEM (the temporary device arrays: up to 17 bytes per row) leaves the sampler usable.  The call is
+ * ordered after everything queued on the sampler's stream and returns when done, like dwx_trace_read; it changes
+ * nothing of the sampler's state.  With the function never called nothing is launched or allocated for it. */
+typedef struct dwx_trace_diag_summary {
+  uint64_t n_entries;       /* entries the statistics are over (= dwx_trace_info's count)           */
+  uint32_t max_lag;         /* as passed                                                            */
+  uint32_t contiguous;      /* 1: the entries' sweep ids are consecutive (no learning sweep between) */
+  uint64_t rows_finite;     /* rows whose rhat is finite                                            */
+  uint64_t rows_constant;   /* rows whose series never changed: rhat and ess are nan                */
+  uint64_t rows_truncated;  /* rows whose autocorrelation sum reached max_lag before Geyer's cut    */
+  uint64_t rows_rhat_above; /* rows with rhat > rhat_threshold (inf counts, nan does not)           */
+  double max_rhat;  uint64_t max_rhat_row;   /* over rows that are not nan; a row attaining it      */
+  double min_ess;   uint64_t min_ess_row;    /* over rows that are not nan; a row attaining it      */
+} dwx_trace_diag_summary;   /* (no row that is not nan: the value is nan, the row UINT64_MAX) */
+int dwx_trace_diagnostics(dwx_sampler *s, uint32_t max_lag, double rhat_threshold, double *rhat, double *ess,
+                          uint8_t *flags, dwx_trace_diag_summary *summary);
 /* assignments_free (chain 0) / assignments_evid (chain 1), original variable order */
 int dwx_get_assignments(dwx_sampler *s, int chain, uint64_t *out);
 int dwx_set_assignments(dwx_sampler *s, int chain, const uint64_t *in);

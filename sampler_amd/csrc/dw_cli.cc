@@ -44,6 +44,7 @@ const FlagSpec kFlags[] = {
     {"", "device", true}, {"", "seed", true}, {"", "step_cap", true}, {"", "plan_layouts", true},
     {"", "gpus", true}, {"", "devices", true}, {"", "comm", true}, {"", "rao_blackwell", false},
     {"", "trace", true}, {"", "trace_vars", true},
+    {"", "diagnostics", false}, {"", "diag_max_lag", true}, {"", "diag_rhat", true},
 };
 
 const FlagSpec *find_flag(const std::string &tok) {
@@ -182,6 +183,9 @@ CmdLine parse_cmdline(int argc, const char *const argv[]) {
     else if (n == "rao_blackwell") a.rao_blackwell = true;
     else if (n == "trace") { if (need_u()) a.trace = u; }
     else if (n == "trace_vars") a.trace_vars = val;
+    else if (n == "diagnostics") a.diagnostics = true;
+    else if (n == "diag_max_lag") { if (need_u()) a.diag_max_lag = u; }
+    else if (n == "diag_rhat") { if (need_d()) a.diag_rhat = d; }
     else if (n == "comm") {
       if (val != "rccl" && val != "host") { ++a.num_errors; err << "PARSE ERROR: Argument: --comm\n             must be rccl or host\n"; }
       a.comm = val;
@@ -198,6 +202,8 @@ CmdLine parse_cmdline(int argc, const char *const argv[]) {
   // -l and -i are required for gibbs (src/cmd_parser.cc:75-80)
   if (is_gibbs && !have_l) { ++a.num_errors; err << "PARSE ERROR:\n             Required argument missing: n_learning_epoch\n"; }
   if (is_gibbs && !have_i) { ++a.num_errors; err << "PARSE ERROR:\n             Required argument missing: n_inference_epoch\n"; }
+  if (a.diagnostics && !a.trace) { ++a.num_errors; err << "PARSE ERROR: Argument: --diagnostics\n             needs --trace N: the diagnostics are computed over the sample trace\n"; }
+  if (a.diagnostics && (a.diag_max_lag < 1 || a.diag_max_lag > 64)) { ++a.num_errors; err << "PARSE ERROR: Argument: --diag_max_lag\n             must be 1 .. 64\n"; }
   // XXX hack of the reference to support two step-size flags (src/cmd_parser.cc:158-160)
   if (a.stepsize == 0.01) a.stepsize = a.stepsize2;
   // n_threads describes CPU threads: accepted and ignored.  n_datacopy > 1 asks for replicas
@@ -241,6 +247,9 @@ std::ostream &operator<<(std::ostream &stream, const CmdLine &args) {
       DWX_ROW("seed", seed),
       {"rao_blackwell", [](std::ostream &o, const CmdLine &a) { o << a.rao_blackwell; }, [](const CmdLine &a) { return a.rao_blackwell; }},
       {"trace", [](std::ostream &o, const CmdLine &a) { o << a.trace; }, [](const CmdLine &a) { return a.trace > 0; }},
+      {"diagnostics", [](std::ostream &o, const CmdLine &a) { o << a.diagnostics; }, [](const CmdLine &a) { return a.diagnostics; }},
+      {"diag_max_lag", [](std::ostream &o, const CmdLine &a) { o << a.diag_max_lag; }, [](const CmdLine &a) { return a.diagnostics; }},
+      {"diag_rhat", [](std::ostream &o, const CmdLine &a) { o << a.diag_rhat; }, [](const CmdLine &a) { return a.diagnostics; }},
   };
 #undef DWX_ROW
 #undef DWX_ROW_LIST
@@ -950,6 +959,46 @@ void dump_trace_to_file(const std::string &path, dwx_sampler *sampler, uint64_t 
   if (!f) throw std::runtime_error("cannot write " + path);
 }
 
+// --diagnostics: split-R-hat and ESS of every value row over the trace, computed on the device
+// (dwx_trace_diagnostics); the rows written are the marginals dump's, in its order
+std::string dump_diagnostics_to_file(const std::string &path, const LoadedGraph &g, bool sample_evidence, dwx_sampler *sampler,
+                                     uint64_t num_values, const uint64_t *var_val_base, const uint64_t *value_sparse,
+                                     uint32_t max_lag, double rhat_threshold) {
+  // (the formatter of the marginal dump, %g; nan and inf spelled the same whatever their sign bit or the C library)
+  auto num = [](double x) {
+    if (x != x) return std::string("nan");
+    if (x - x != 0.0) return std::string(x > 0 ? "inf" : "-inf");
+    char tmp[64];
+    return std::string(tmp, (size_t)snprintf(tmp, sizeof tmp, "%g", x));
+  };
+  dwx::RawArray<double> rhat(num_values), ess(num_values);
+  dwx::RawArray<uint8_t> flags(num_values);
+  dwx_trace_diag_summary sm;
+  if (dwx_trace_diagnostics(sampler, max_lag, rhat_threshold, rhat.data(), ess.data(), flags.data(), &sm) != DWX_OK)
+    throw std::runtime_error(dwx_last_error());
+  auto row_id = [](uint64_t r) { return r == ~0ull ? std::string("-1") : std::to_string(r); };
+  const std::string head = "# n_entries=" + std::to_string(sm.n_entries) + " max_lag=" + std::to_string(sm.max_lag) +
+      " contiguous=" + std::to_string(sm.contiguous) + " rows_finite=" + std::to_string(sm.rows_finite) +
+      " rows_constant=" + std::to_string(sm.rows_constant) + " rows_truncated=" + std::to_string(sm.rows_truncated) +
+      " rows_rhat_above=" + std::to_string(sm.rows_rhat_above) + " max_rhat=" + num(sm.max_rhat) +
+      " max_rhat_row=" + row_id(sm.max_rhat_row) + " min_ess=" + num(sm.min_ess) + " min_ess_row=" + row_id(sm.min_ess_row);
+  std::string s = head + "\n";
+  for (uint64_t v = 0; v < g.n_variables; ++v) {
+    if (g.var_role[v] >= 1 && !sample_evidence) continue;
+    const uint64_t b = var_val_base[v], rows = g.var_dtype[v] == 0 ? 1 : g.var_cardinality[v];
+    for (uint64_t j = 0; j < rows; ++j) {
+      append_u64(s, v); s.push_back(' ');
+      append_u64(s, g.var_dtype[v] == 0 ? 1 : value_sparse[b + j]);
+      s += " " + num(rhat[b + j]) + " " + num(ess[b + j]) + " ";
+      append_u64(s, flags[b + j]); s.push_back('\n');
+    }
+  }
+  std::ofstream f(path, std::ios::binary);
+  f.write(s.data(), (std::streamsize)s.size());
+  if (!f) throw std::runtime_error("cannot write " + path);
+  return head;
+}
+
 // Graph-compile options of a `dw gibbs` run.  Ordering the variables of an all-unary graph by the
 // weight of their first record makes a sweep ~5 % faster and the host-side build
 // much slower -- the records are then gathered in a random order: 10 s of a 42 s run at config 5's
@@ -1206,6 +1255,16 @@ int gibbs(const CmdLine &args) {
         std::cout << "DUMPING... TEXT    : " << fn << std::endl;
         dump_trace_to_file(fn, sampler, V, args.trace_vars);
         phase("dump trace");
+      }
+      if (args.diagnostics) {
+        // --diagnostics: "# name=value ..." (the summary), then "vid value rhat ess flags" per row of the
+        // marginals dump.  No reference counterpart (it keeps counts only, src/gibbs_sampler.h:160-167).
+        fn = args.output_folder + "/inference_result.out.diagnostics.text";
+        std::cout << "DUMPING... TEXT    : " << fn << std::endl;
+        const std::string line = dump_diagnostics_to_file(fn, lg, args.should_sample_evidence, sampler, info.num_values, base.data(),
+                                                          sparse.data(), (uint32_t)args.diag_max_lag, args.diag_rhat);
+        if (!args.should_be_quiet) std::cout << "TRACE DIAGNOSTICS  : " << line.substr(2) << std::endl;
+        phase("dump diagnostics");
       }
       if (progress) {
         // the reference's closing calibration table (InferenceResult::show_marginal_histogram,

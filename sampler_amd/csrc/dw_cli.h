@@ -47,6 +47,9 @@ struct CmdLine {
   uint64_t trace = 0;           // --trace N: keep the last N inference sweeps' joint assignments (dwx_trace_enable) and
   std::string trace_vars;       // write them, for --trace_vars FILE's variables (one id per line; default: all), to
                                 // <out>/inference_result.out.trace.text.  Single rank only.
+  bool diagnostics = false;     // --diagnostics (with --trace): split-R-hat and ESS of every dumped value row over the
+  uint64_t diag_max_lag = 64;   // trace, computed on the device (dwx_trace_diagnostics; --diag_max_lag 1 .. 64), to
+  double diag_rhat = 1.01;      // <out>/inference_result.out.diagnostics.text; --diag_rhat: the summary's threshold
   int num_errors = 0;
   std::string error_text;
 };
@@ -102,6 +105,11 @@ void dump_marginals_to_file(const std::string &path, const LoadedGraph &g, bool 
 
 // --trace (dw_cli.cc): "# sweeps: id ..." then "vid <tab> v v ..." per selected variable, oldest sweep first
 void dump_trace_to_file(const std::string &path, dwx_sampler *sampler, uint64_t n_variables, const std::string &vars_file);
+// --diagnostics (dw_cli.cc): "# name=value ..." (dwx_trace_diag_summary), then "vid value rhat ess flags" per row of
+// every variable the marginals dump lists, in its order; returns the summary line
+std::string dump_diagnostics_to_file(const std::string &path, const LoadedGraph &g, bool sample_evidence, dwx_sampler *sampler,
+                                     uint64_t num_values, const uint64_t *var_val_base, const uint64_t *value_sparse,
+                                     uint32_t max_lag, double rhat_threshold);
 
 // graph-compile options of a run (dw_cli.cc: the weight order of the variables only for long runs)
 dwx_compile_opts compile_opts_for(const CmdLine &args);

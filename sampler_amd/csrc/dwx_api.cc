@@ -24,6 +24,7 @@
 #include "host_parallel.h"
 
 #include "sweep_kernels.h"   // (device_intrinsics.h: the HIP runtime shim rt_hip.h comes with it)
+#include "diag_kernels.h"    // (dwx_trace_diagnostics)
 
 // a finer cut must lower the batches' curvature estimate to this fraction, else the plan stops
 // (dwx_sgd_plan; multi-GPU drivers apply the same rule to the global estimate)
@@ -2579,6 +2580,96 @@ int dwx_trace_read(dwx_sampler *s, uint64_t first_entry, uint64_t n_entries, con
     }
     rt::dfree(d_pos); rt::dfree(d_out);
   });
+}
+
+int dwx_trace_diagnostics(dwx_sampler *s, uint32_t max_lag, double rhat_threshold, double *rhat, double *ess,
+                          uint8_t *flags, dwx_trace_diag_summary *summary) {
+  if (!s) return fail(DWX_E_INVALID, "null sampler");
+  if (!s->d_trace) return fail(DWX_E_INVALID, "the sample trace was never enabled (dwx_trace_enable)");
+  if (s->trace_count < 4) return fail(DWX_E_INVALID, "split-R-hat needs at least 4 entries in the sample trace");
+  if (max_lag < 1 || max_lag > DIAG_MAX_LAG) return fail(DWX_E_INVALID, "max_lag must be 1 .. 64");
+  if (!rhat && !ess && !flags && !summary) return fail(DWX_E_INVALID, "null argument: nothing to return");
+  if (s->trace_count > 0x7FFFFFFFu) return fail(DWX_E_LIMIT, "the diagnostics take at most 2^31 - 1 entries");
+  const CompiledGraph &c = *s->cg;
+  const uint32_t n = s->trace_count, n_rows = c.v_row[c.Vo];
+  const uint32_t slot0 = (uint32_t)(((uint64_t)s->trace_next + s->trace_cap - n) % s->trace_cap);
+  const bool bit = s->trace_bits == 1;
+  const unsigned block = bit ? DIAG_BIT_THREADS : DIAG_BYTE_THREADS;
+  const unsigned grid = bit ? (s->trace_words + block / 64u - 1u) / (block / 64u) : (n_rows + block - 1u) / block;
+  if (!grid) return fail(DWX_E_INVALID, "no owned variables");
+  bool nomem = false;
+  unsigned long long counts[4] = {0, 0, 0, 0};
+  DiagPartial best;
+  int rc = guarded([&]() {
+    rt::set_device(s->device);
+    void *d_rhat = nullptr, *d_ess = nullptr, *d_flags = nullptr, *d_counts = nullptr, *d_part = nullptr;
+    auto release = [&]() { rt::dfree(d_rhat); rt::dfree(d_ess); rt::dfree(d_flags); rt::dfree(d_counts); rt::dfree(d_part); };
+    try {
+      d_counts = optional_dmalloc(sizeof(counts));
+      d_part = optional_dmalloc((size_t)grid * sizeof(DiagPartial));
+      if (rhat) d_rhat = optional_dmalloc((size_t)n_rows * 8);
+      if (ess) d_ess = optional_dmalloc((size_t)n_rows * 8);
+      if (flags) d_flags = optional_dmalloc(n_rows);
+      if (!d_counts || !d_part || (rhat && !d_rhat) || (ess && !d_ess) || (flags && !d_flags)) {
+        nomem = true;
+        release();
+        return;
+      }
+      rt::dmemset(d_counts, 0, sizeof(counts), s->stream);
+      auto go = [&](auto kernel) {
+        rt::launch(kernel, grid, block, 0, s->stream, (const unsigned long long *)s->d_trace, s->trace_words, s->trace_cap,
+                   slot0, n, (uint32_t)c.Vo, n_rows, (const uint32_t *)s->d_v_row, (const uint32_t *)s->d_v_meta, max_lag,
+                   rhat_threshold, (double *)d_rhat, (double *)d_ess, (unsigned char *)d_flags,
+                   (unsigned long long *)d_counts, (DiagPartial *)d_part);
+      };
+      if (bit) go(trace_diag_kernel<1>); else go(trace_diag_kernel<8>);
+      rt::launch(trace_diag_fold_kernel, 1u, BLOCK_THREADS, 0, s->stream, (DiagPartial *)d_part, (uint32_t)grid);
+      rt::d2h(counts, d_counts, sizeof(counts), s->stream);
+      rt::d2h(&best, d_part, sizeof(best), s->stream);
+      // device row order -> the reference numbering: the tallies' translation
+      auto fetch = [&](auto *out, const void *d_arr) {
+        typedef typename std::remove_pointer<decltype(out)>::type T;
+        RawArray<T> t(n_rows);
+        rt::d2h(t.data(), d_arr, (size_t)n_rows * sizeof(T), s->stream);
+        rt::stream_sync(s->stream);
+        parallel_ranges(c.Vo, host_threads(), [&](uint64_t pb, uint64_t pe) {
+          for (uint64_t p = pb; p < pe; ++p) {
+            const uint64_t rb = c.ref_var_val_base[c.perm[p]];
+            for (uint32_t r = c.v_row[p]; r < c.v_row[p + 1]; ++r) out[rb + (r - c.v_row[p])] = t[r];
+          }
+        });
+      };
+      if (rhat) fetch(rhat, d_rhat);
+      if (ess) fetch(ess, d_ess);
+      if (flags) fetch(flags, d_flags);
+      rt::stream_sync(s->stream);
+    } catch (...) {
+      release();
+      throw;
+    }
+    release();
+  });
+  if (rc != DWX_OK) return rc;
+  if (nomem) return fail(DWX_E_NOMEM, "no device memory for the diagnostics' temporary arrays (up to 17 bytes per value row)");
+  if (summary) {
+    auto ref_row = [&](uint32_t r) -> uint64_t {
+      if (r == DIAG_NO_ROW) return ~0ull;
+      const uint32_t *first = c.v_row.data();
+      const uint64_t p = (uint64_t)(std::upper_bound(first, first + c.Vo + 1, r) - first) - 1;   // v_row[p] <= r < v_row[p + 1]
+      return c.ref_var_val_base[c.perm[p]] + (r - c.v_row[p]);
+    };
+    summary->n_entries = n;
+    summary->max_lag = max_lag;
+    summary->contiguous = 1;
+    for (uint32_t e = 1; e < n; ++e)
+      if (s->trace_ids[(slot0 + e) % s->trace_cap] != s->trace_ids[(slot0 + e - 1) % s->trace_cap] + 1) summary->contiguous = 0;
+    summary->rows_finite = counts[0]; summary->rows_constant = counts[1];
+    summary->rows_truncated = counts[2]; summary->rows_rhat_above = counts[3];
+    const double nan = std::nan("");
+    summary->max_rhat = best.max_row == DIAG_NO_ROW ? nan : best.max_rhat; summary->max_rhat_row = ref_row(best.max_row);
+    summary->min_ess = best.min_row == DIAG_NO_ROW ? nan : best.min_ess; summary->min_ess_row = ref_row(best.min_row);
+  }
+  return DWX_OK;
 }
 
 int dwx_get_tallies(dwx_sampler *s, uint64_t *tallies, uint64_t *nsamples) {

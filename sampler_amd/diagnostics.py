@@ -5,6 +5,11 @@ different seeds on the same Graph; a chain's draws are the rows of GibbsSampler.
 variable), cast to float.  A quantity whose draws have zero variance (a boolean variable that never flipped,
 evidence) has no defined ratio: both functions return nan for it, without a warning.
 
+This module is the route for a selection of variables and for several chains: ess is a Python loop per quantity.
+For every value row of a whole graph (one chain) the same two numbers are computed on the device, from the trace
+where it lies: GibbsSampler.trace_diagnostics (include/dwx.h: dwx_trace_diagnostics), which equals split_rhat / ess
+of x[1, draws, rows] here with the rows' 0 / 1 indicator series.
+
 Formulas: Gelman, Carlin, Stern, Dunson, Vehtari, Rubin, "Bayesian Data Analysis", 3rd ed., section 11.4-11.5.
 """
 import numpy as np

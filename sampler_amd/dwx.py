@@ -29,7 +29,7 @@ SYMBOLS = [
     "dwx_sgd_apply_async", "dwx_sgd_finish",
     "dwx_get_weights", "dwx_set_weights", "dwx_average_weights_async",
     "dwx_clear_tallies", "dwx_get_tallies", "dwx_rb_enable", "dwx_get_rb_sums",
-    "dwx_trace_enable", "dwx_trace_info", "dwx_trace_read",
+    "dwx_trace_enable", "dwx_trace_info", "dwx_trace_read", "dwx_trace_diagnostics",
     "dwx_get_assignments", "dwx_set_assignments", "dwx_get_sweep", "dwx_set_sweep",
     "dwx_device_buffer", "dwx_halo_create", "dwx_halo_destroy", "dwx_halo_buffer", "dwx_halo_message_bytes", "dwx_halo_pack_async",
     "dwx_halo_unpack_async", "dwx_stream", "dwx_kernel_time", "dwx_kernel_time_reset",
@@ -41,6 +41,14 @@ class DwxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("dwx error %d: %s" % (code, msg))
         self.code = code
+
+
+class TraceDiagSummary(C.Structure):
+    """dwx_trace_diag_summary (include/dwx.h)"""
+    _fields_ = [("n_entries", C.c_uint64), ("max_lag", C.c_uint32), ("contiguous", C.c_uint32),
+                ("rows_finite", C.c_uint64), ("rows_constant", C.c_uint64), ("rows_truncated", C.c_uint64),
+                ("rows_rhat_above", C.c_uint64), ("max_rhat", C.c_double), ("max_rhat_row", C.c_uint64),
+                ("min_ess", C.c_double), ("min_ess_row", C.c_uint64)]
 
 
 class CompileOpts(C.Structure):
@@ -124,6 +132,7 @@ class Library:
         L.dwx_trace_enable.argtypes = [vp, C.c_uint32]
         L.dwx_trace_info.argtypes = [vp, vp, vp, vp]
         L.dwx_trace_read.argtypes = [vp, u64, u64, vp, u64, vp]
+        L.dwx_trace_diagnostics.argtypes = [vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
         L.dwx_get_assignments.argtypes = [vp, i32, vp]
         L.dwx_set_assignments.argtypes = [vp, i32, vp]
         L.dwx_get_sweep.argtypes = [vp, vp]; L.dwx_set_sweep.argtypes = [vp, u64]
@@ -408,6 +417,24 @@ class GibbsSampler:
         for col, v in enumerate(vids):
             out.append("%d\t%s\n" % (int(v), " ".join("%d" % x for x in t[:, col].tolist())) if len(ids) else "%d\n" % int(v))
         return "".join(out)
+
+    def trace_diagnostics(self, max_lag=64, rhat_threshold=1.01, arrays=True):
+        """Split-R-hat and effective sample size of every value row over the entries the trace holds, computed on
+        the device (include/dwx.h: dwx_trace_diagnostics states the definition; single chain, indicator series).
+        -> (float64[num_values] rhat, float64[num_values] ess, uint8[num_values] flags (bit 0 constant, bit 1
+        truncated at max_lag), summary dict of dwx_trace_diag_summary's fields), rows in the reference numbering
+        as `tallies()`; ghost variables' rows are nan / 0.  arrays=False: (None, None, None, summary), only the
+        summary crosses to the host."""
+        summ = TraceDiagSummary()
+        rhat = ess = flags = None
+        if arrays:
+            rhat = np.full(self.num_values, np.nan)
+            ess = np.full(self.num_values, np.nan)
+            flags = np.zeros(self.num_values, np.uint8)
+        self.lib.check(self.lib.L.dwx_trace_diagnostics(
+            self.h, int(max_lag), float(rhat_threshold), rhat.ctypes.data if arrays else None,
+            ess.ctypes.data if arrays else None, flags.ctypes.data if arrays else None, C.addressof(summ)))
+        return rhat, ess, flags, {name: getattr(summ, name) for name, _ in TraceDiagSummary._fields_}
 
     def assignments(self, chain):
         out = np.zeros(self.V, np.uint64)

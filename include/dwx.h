@@ -359,7 +359,8 @@ int dwx_get_rb_sums(dwx_sampler *s, uint64_t *sums, uint64_t *nsamples);
  *                        range outside the entries held, on a ghost or unknown id.
  *   dwx_clear_tallies    empties the trace with the tallies: while count <= capacity, the number of entries
  *                        with value d equals tallies[row0 + d] for every sampled variable.
- * With the trace off nothing is launched or allocated for it. */
+ * With the trace off nothing is launched or allocated for it.  Both uses have a device path that reads the ring
+ * where it lies: dwx_trace_diagnostics (the sequences) and dwx_trace_cooccurrence (the joint counts), below. */
 int dwx_trace_enable(dwx_sampler *s, uint32_t capacity_sweeps);
 int dwx_trace_info(dwx_sampler *s, uint64_t *count, uint64_t *capacity, uint64_t *sweep_ids);
 int dwx_trace_read(dwx_sampler *s, uint64_t first_entry, uint64_t n_entries, const uint64_t *vids, uint64_t n_vids,
@@ -407,6 +408,39 @@ typedef struct dwx_trace_diag_summary {
 } dwx_trace_diag_summary;   /* (no row that is not nan: the value is nan, the row UINT64_MAX) */
 int dwx_trace_diagnostics(dwx_sampler *s, uint32_t max_lag, double rhat_threshold, double *rhat, double *ess,
                           uint8_t *flags, dwx_trace_diag_summary *summary);
+/* Joint counts of PAIRS of value rows over the sample trace, counted on the device from the ring where it lies.
+ * NO reference counterpart: the reference keeps counts only (sample_single_variable, src/gibbs_sampler.h:160-167)
+ * and overwrites every assignment with the next, so it cannot tell whether two things were true TOGETHER.
+ * dwx_trace_read ships a byte per (entry, variable) to the host for that; this call ships the pairs up and three
+ * integers per pair down.
+ * Rows are value rows in the REFERENCE numbering, as in dwx_get_tallies, dwx_graph_get_values and
+ * dwx_trace_diagnostics: a boolean variable has one row, the indicator of value 1; a categorical variable one row per
+ * dense value d, the indicator x == d.  A row's series x_r(e) is exactly the series dwx_trace_diagnostics defines
+ * for it; an unsampled owned variable has one too (whatever the trace holds for it).  A ghost variable has no value
+ * rows at all (num_values counts the owned variables' rows), so none of its can be named.
+ * Definition.  E = [first_entry, first_entry + n_entries), entry 0 the oldest held (as dwx_trace_read).  For pair i:
+ *   n_ab[i] = #{e in E: x_{rows_a[i]}(e) = 1 and x_{rows_b[i]}(e) = 1},
+ *   n_a[i]  = #{e in E: x_{rows_a[i]}(e) = 1},   n_b[i] = #{e in E: x_{rows_b[i]}(e) = 1}.
+ * n_a and n_b may each be null; n_ab may not.  P(a and b) = n_ab / n_entries, P(a and not b) = (n_a - n_ab) /
+ * n_entries, lift, phi and the like are the caller's (sampler_amd/diagnostics.py: cooccurrence_stats): the library
+ * returns integers only.  Pairs may repeat; rows_a[i] == rows_b[i] is allowed (n_ab == n_a == n_b); two different
+ * values of one categorical variable give n_ab == 0.  While count <= capacity after dwx_clear_tallies, n_a over all
+ * entries equals tallies[rows_a[i]] for a sampled variable's row.
+ * n_entries == 0 (a valid range) returns DWX_OK and zeroes every output; n_pairs == 0 returns DWX_OK and touches
+ * nothing, whatever the pointers.
+ * DWX_E_INVALID: trace never enabled; first_entry + n_entries > count (dwx_trace_info); n_ab, rows_a or rows_b null
+ * with n_pairs > 0; a row >= num_values (a ghost variable has no rows: there is no other "ghost row" case).
+ * DWX_E_LIMIT: n_entries > 2^31 - 1 or a ring of more than 2^31 - 1 sweeps (the kernel's counts and plane cursor are
+ * 32-bit); n_pairs > 2^32 - 1 (a bound of the call, not of the kernel, whose pair index is 64-bit: the temporary
+ * arrays of such a call would exceed 146 GB -- split the list).
+ * DWX_E_NOMEM (the temporary device arrays: up to 34 bytes per pair) leaves the sampler usable.  After any error
+ * return the output arrays are as they were.  Each row is translated to a (device position, dense value) once per
+ * call on the host; only the translated pairs go up (8 or 10 bytes per pair) and 3 x 8 x n_pairs bytes come down.
+ * The call is ordered after everything queued on the sampler's stream and returns when done, like dwx_trace_read;
+ * it changes nothing of the sampler's state.  With the function never called nothing is launched or allocated for
+ * it. */
+int dwx_trace_cooccurrence(dwx_sampler *s, const uint64_t *rows_a, const uint64_t *rows_b, uint64_t n_pairs,
+                           uint64_t first_entry, uint64_t n_entries, uint64_t *n_ab, uint64_t *n_a, uint64_t *n_b);
 /* assignments_free (chain 0) / assignments_evid (chain 1), original variable order */
 int dwx_get_assignments(dwx_sampler *s, int chain, uint64_t *out);
 int dwx_set_assignments(dwx_sampler *s, int chain, const uint64_t *in);

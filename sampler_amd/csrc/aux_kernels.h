@@ -578,6 +578,63 @@ trace_gather_kernel(const unsigned long long *ring, uint32_t words, uint32_t cap
   }
 }
 
+// dwx_trace_cooccurrence: joint counts of pairs of value rows over n_entries entries of the ring, entry 0 at plane
+// slot0 (NO reference counterpart: the reference keeps counts only, src/gibbs_sampler.h:160-167).  Pair i is the
+// positions pos_a[i], pos_b[i] and, BITS = 8, the dense values val_a[i], val_b[i] its two rows are the indicators of
+// (a boolean variable's row: 1); BITS = 1 ignores the values (every row is "the bit is set").  The host translated
+// the rows once per call.  out[i], out[n_pairs + i], out[2 n_pairs + i] = the entries where both indicators are 1,
+// where a's is, where b's is.
+// A LANE OWNS A PAIR and keeps its three counts in registers; pairs are walked grid-stride and, within a pass, every
+// lane of the grid walks the entries in the same order, oldest first -- the waves resident together read the same
+// few planes, which stay in the XCD's L2 while they are needed (a plane of 10 M booleans is 1.25 MB).  The entry
+// loop is unrolled COOC_UNROLL times: 2 x COOC_UNROLL independent gathers in flight per lane.  One writer per pair:
+// plain coalesced stores, no atomics, no ballots (so no whole-workgroup convergence under the emulation either).
+// Counts are 32-bit: n_entries <= the ring's capacity < 2^32.
+constexpr uint32_t COOC_UNROLL = 8;
+constexpr uint32_t COOC_MAX_BLOCKS = 512;   // the grid's cap: two workgroups per CU, 16 gathers in flight per lane
+template <int BITS>
+DWX_DEV uint32_t trace_cooc_bit(const unsigned long long *plane, uint32_t p, uint32_t d) {
+  if (BITS == 1) return (uint32_t)(plane[p >> 6] >> (p & 63u)) & 1u;
+  return ((const unsigned char *)plane)[p] == d ? 1u : 0u;
+}
+template <int BITS>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+trace_cooc_kernel(const unsigned long long *ring, uint32_t words, uint32_t cap, uint32_t slot0, uint32_t n_entries,
+                  const uint32_t *pos_a, const uint32_t *pos_b, const unsigned char *val_a, const unsigned char *val_b,
+                  uint64_t n_pairs, unsigned long long *out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pairs; i += stride) {
+    const uint32_t pa = pos_a[i], pb = pos_b[i];
+    const uint32_t da = BITS == 8 ? val_a[i] : 1u, db = BITS == 8 ? val_b[i] : 1u;
+    uint32_t n_ab = 0, n_a = 0, n_b = 0;
+    uint32_t slot = slot0, e = 0;                  // slot = (slot0 + e) mod cap, slot0 < cap
+    for (; e + COOC_UNROLL <= n_entries; e += COOC_UNROLL) {
+      uint32_t xa[COOC_UNROLL], xb[COOC_UNROLL];
+#pragma unroll
+      for (uint32_t u = 0; u < COOC_UNROLL; ++u) {
+        uint32_t su = slot + u;                    // (u < COOC_UNROLL <= n_entries <= cap: one wrap at the most)
+        if (su >= cap) su -= cap;
+        const unsigned long long *plane = ring + (size_t)su * words;
+        xa[u] = trace_cooc_bit<BITS>(plane, pa, da);
+        xb[u] = trace_cooc_bit<BITS>(plane, pb, db);
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < COOC_UNROLL; ++u) { n_ab += xa[u] & xb[u]; n_a += xa[u]; n_b += xb[u]; }
+      slot += COOC_UNROLL;
+      if (slot >= cap) slot -= cap;
+    }
+    for (; e < n_entries; ++e) {
+      const unsigned long long *plane = ring + (size_t)slot * words;
+      const uint32_t x = trace_cooc_bit<BITS>(plane, pa, da), y = trace_cooc_bit<BITS>(plane, pb, db);
+      n_ab += x & y; n_a += x; n_b += y;
+      if (++slot == cap) slot = 0;
+    }
+    out[i] = n_ab;
+    out[n_pairs + i] = n_a;
+    out[2 * n_pairs + i] = n_b;
+  }
+}
+
 // test hook: the raw Philox4x32-10 block function and the two uniforms drawn from it, on the
 // device (Random123 known-answer vectors; tests/test_philox_kat.py)
 __global__ void test_philox_kernel(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,

@@ -45,6 +45,7 @@ const FlagSpec kFlags[] = {
     {"", "gpus", true}, {"", "devices", true}, {"", "comm", true}, {"", "rao_blackwell", false},
     {"", "trace", true}, {"", "trace_vars", true},
     {"", "diagnostics", false}, {"", "diag_max_lag", true}, {"", "diag_rhat", true},
+    {"", "trace_pairs", true},
 };
 
 const FlagSpec *find_flag(const std::string &tok) {
@@ -186,6 +187,7 @@ CmdLine parse_cmdline(int argc, const char *const argv[]) {
     else if (n == "diagnostics") a.diagnostics = true;
     else if (n == "diag_max_lag") { if (need_u()) a.diag_max_lag = u; }
     else if (n == "diag_rhat") { if (need_d()) a.diag_rhat = d; }
+    else if (n == "trace_pairs") a.trace_pairs = val;
     else if (n == "comm") {
       if (val != "rccl" && val != "host") { ++a.num_errors; err << "PARSE ERROR: Argument: --comm\n             must be rccl or host\n"; }
       a.comm = val;
@@ -204,6 +206,7 @@ CmdLine parse_cmdline(int argc, const char *const argv[]) {
   if (is_gibbs && !have_i) { ++a.num_errors; err << "PARSE ERROR:\n             Required argument missing: n_inference_epoch\n"; }
   if (a.diagnostics && !a.trace) { ++a.num_errors; err << "PARSE ERROR: Argument: --diagnostics\n             needs --trace N: the diagnostics are computed over the sample trace\n"; }
   if (a.diagnostics && (a.diag_max_lag < 1 || a.diag_max_lag > 64)) { ++a.num_errors; err << "PARSE ERROR: Argument: --diag_max_lag\n             must be 1 .. 64\n"; }
+  if (!a.trace_pairs.empty() && !a.trace) { ++a.num_errors; err << "PARSE ERROR: Argument: --trace_pairs\n             needs --trace N: the joint counts are taken over the sample trace\n"; }
   // XXX hack of the reference to support two step-size flags (src/cmd_parser.cc:158-160)
   if (a.stepsize == 0.01) a.stepsize = a.stepsize2;
   // n_threads describes CPU threads: accepted and ignored.  n_datacopy > 1 asks for replicas
@@ -250,6 +253,7 @@ std::ostream &operator<<(std::ostream &stream, const CmdLine &args) {
       {"diagnostics", [](std::ostream &o, const CmdLine &a) { o << a.diagnostics; }, [](const CmdLine &a) { return a.diagnostics; }},
       {"diag_max_lag", [](std::ostream &o, const CmdLine &a) { o << a.diag_max_lag; }, [](const CmdLine &a) { return a.diagnostics; }},
       {"diag_rhat", [](std::ostream &o, const CmdLine &a) { o << a.diag_rhat; }, [](const CmdLine &a) { return a.diagnostics; }},
+      {"trace_pairs", [](std::ostream &o, const CmdLine &a) { o << a.trace_pairs; }, [](const CmdLine &a) { return !a.trace_pairs.empty(); }},
   };
 #undef DWX_ROW
 #undef DWX_ROW_LIST
@@ -999,6 +1003,69 @@ std::string dump_diagnostics_to_file(const std::string &path, const LoadedGraph 
   return head;
 }
 
+// --trace_pairs: the file's lines -> (variable, value) pairs and their value rows
+TracePairs load_trace_pairs(const std::string &file, const LoadedGraph &g, const uint64_t *var_val_base,
+                            const uint64_t *value_sparse) {
+  std::ifstream in(file);
+  if (!in) throw std::runtime_error("--trace_pairs: cannot open " + file);
+  TracePairs tp;
+  std::string line;
+  for (uint64_t ln = 1; getline(in, line); ++ln) {
+    auto bad = [&](const std::string &why) {
+      return std::runtime_error("--trace_pairs: line " + std::to_string(ln) + ": " + why + ": '" + line + "'");
+    };
+    std::istringstream ss(line);
+    std::string tok;
+    uint64_t f[4];
+    size_t nf = 0;
+    while (ss >> tok) {
+      if (nf == 4 || !to_u64(tok, f[nf])) throw bad("expected 'vid_a vid_b' or 'vid_a value_a vid_b value_b'");
+      ++nf;
+    }
+    if (nf == 0) continue;
+    if (nf != 2 && nf != 4) throw bad("expected 'vid_a vid_b' or 'vid_a value_a vid_b value_b'");
+    const uint64_t vid[2] = {f[0], nf == 2 ? f[1] : f[2]}, value[2] = {nf == 2 ? 1 : f[1], nf == 2 ? 1 : f[3]};
+    uint64_t row[2];
+    for (int k = 0; k < 2; ++k) {
+      const uint64_t v = vid[k];
+      if (v >= g.n_variables) throw bad("unknown variable " + std::to_string(v));
+      if (g.var_dtype[v] == 0) {
+        if (value[k] != 1) throw bad("a boolean variable's value is 1");
+        row[k] = var_val_base[v];
+      } else {
+        if (nf == 2) throw bad("variable " + std::to_string(v) + " is categorical: give its value");
+        uint64_t j = 0;
+        while (j < g.var_cardinality[v] && value_sparse[var_val_base[v] + j] != value[k]) ++j;
+        if (j == g.var_cardinality[v]) throw bad("variable " + std::to_string(v) + " has no value " + std::to_string(value[k]));
+        row[k] = var_val_base[v] + j;
+      }
+    }
+    tp.vid_a.push_back(vid[0]); tp.value_a.push_back(value[0]); tp.row_a.push_back(row[0]);
+    tp.vid_b.push_back(vid[1]); tp.value_b.push_back(value[1]); tp.row_b.push_back(row[1]);
+  }
+  return tp;
+}
+
+// --trace_pairs: the pairs' joint counts over every entry the ring holds, counted on the device (dwx_trace_cooccurrence)
+void dump_pairs_to_file(const std::string &path, dwx_sampler *sampler, const TracePairs &pairs) {
+  auto ok = [](int rc) { if (rc != DWX_OK) throw std::runtime_error(dwx_last_error()); };
+  uint64_t count = 0;
+  ok(dwx_trace_info(sampler, &count, nullptr, nullptr));
+  const size_t n = pairs.row_a.size();
+  std::vector<uint64_t> n_ab(n), n_a(n), n_b(n);
+  ok(dwx_trace_cooccurrence(sampler, pairs.row_a.data(), pairs.row_b.data(), n, 0, count, n_ab.data(), n_a.data(), n_b.data()));
+  std::string s = "# entries=" + std::to_string(count) + "\n";
+  for (size_t i = 0; i < n; ++i) {
+    for (uint64_t x : {pairs.vid_a[i], pairs.value_a[i], pairs.vid_b[i], pairs.value_b[i], n_ab[i], n_a[i]}) {
+      append_u64(s, x); s.push_back(' ');
+    }
+    append_u64(s, n_b[i]); s.push_back('\n');
+  }
+  std::ofstream f(path, std::ios::binary);
+  f.write(s.data(), (std::streamsize)s.size());
+  if (!f) throw std::runtime_error("cannot write " + path);
+}
+
 // Graph-compile options of a `dw gibbs` run.  Ordering the variables of an all-unary graph by the
 // weight of their first record makes a sweep ~5 % faster and the host-side build
 // much slower -- the records are then gathered in a random order: 10 s of a 42 s run at config 5's
@@ -1107,6 +1174,14 @@ int gibbs(const CmdLine &args) {
                 << ") #F=" << lg.n_factors << " #W=" << lg.n_weights << " #E=" << lg.n_edges
                 << " #Val=" << info.num_values << std::endl;
     };
+    // --trace_pairs FILE: read and checked before anything is sampled or written
+    TracePairs pairs;
+    if (!args.trace_pairs.empty()) {
+      dwx::RawArray<uint64_t> base(lg.n_variables), sparse(info.num_values);
+      ok(dwx_graph_get_values(graph, base.data(), sparse.data()));
+      pairs = load_trace_pairs(args.trace_pairs, lg, base.data(), sparse.data());
+      phase("load pairs");
+    }
     print_size("Factor graph loaded:\t");
     print_size("Factor graph indexed:\t");
     if (!args.should_be_quiet)
@@ -1265,6 +1340,15 @@ int gibbs(const CmdLine &args) {
                                                           sparse.data(), (uint32_t)args.diag_max_lag, args.diag_rhat);
         if (!args.should_be_quiet) std::cout << "TRACE DIAGNOSTICS  : " << line.substr(2) << std::endl;
         phase("dump diagnostics");
+      }
+      if (!args.trace_pairs.empty()) {
+        // --trace_pairs FILE: "# entries=<n>", then "vid_a value_a vid_b value_b n_ab n_a n_b" per listed pair in input
+        // order: the entries of the trace where both hold, where each one does.  Integers only.  No reference
+        // counterpart (it keeps counts only, src/gibbs_sampler.h:160-167).
+        fn = args.output_folder + "/inference_result.out.pairs.text";
+        std::cout << "DUMPING... TEXT    : " << fn << std::endl;
+        dump_pairs_to_file(fn, sampler, pairs);
+        phase("dump pairs");
       }
       if (progress) {
         // the reference's closing calibration table (InferenceResult::show_marginal_histogram,

@@ -50,6 +50,8 @@ struct CmdLine {
   bool diagnostics = false;     // --diagnostics (with --trace): split-R-hat and ESS of every dumped value row over the
   uint64_t diag_max_lag = 64;   // trace, computed on the device (dwx_trace_diagnostics; --diag_max_lag 1 .. 64), to
   double diag_rhat = 1.01;      // <out>/inference_result.out.diagnostics.text; --diag_rhat: the summary's threshold
+  std::string trace_pairs;      // --trace_pairs FILE (with --trace): joint counts of the listed (variable, value) pairs over the
+                                // trace, counted on the device (dwx_trace_cooccurrence), to <out>/inference_result.out.pairs.text
   int num_errors = 0;
   std::string error_text;
 };
@@ -110,6 +112,19 @@ void dump_trace_to_file(const std::string &path, dwx_sampler *sampler, uint64_t 
 std::string dump_diagnostics_to_file(const std::string &path, const LoadedGraph &g, bool sample_evidence, dwx_sampler *sampler,
                                      uint64_t num_values, const uint64_t *var_val_base, const uint64_t *value_sparse,
                                      uint32_t max_lag, double rhat_threshold);
+
+// --trace_pairs (dw_cli.cc).  A line of the file is "vid_a vid_b" (value 1 of two boolean variables) or "vid_a value_a
+// vid_b value_b", values as the marginals dump prints them (1 for a boolean variable, the sparse domain value for a
+// categorical one); blank lines are skipped.  Anything else on a line, an unknown variable or value, and value 0 of a
+// boolean variable throw std::runtime_error naming the line.
+struct TracePairs {
+  std::vector<uint64_t> vid_a, value_a, vid_b, value_b;   // as read (the two-field form: values 1)
+  std::vector<uint64_t> row_a, row_b;                     // their value rows (reference numbering)
+};
+TracePairs load_trace_pairs(const std::string &file, const LoadedGraph &g, const uint64_t *var_val_base,
+                            const uint64_t *value_sparse);
+// "# entries=<n>" then "vid_a value_a vid_b value_b n_ab n_a n_b" per pair, in input order, over all entries held
+void dump_pairs_to_file(const std::string &path, dwx_sampler *sampler, const TracePairs &pairs);
 
 // graph-compile options of a run (dw_cli.cc: the weight order of the variables only for long runs)
 dwx_compile_opts compile_opts_for(const CmdLine &args);

@@ -734,6 +734,7 @@ int gibbs_multi(const CmdLine &args) {
   int exit_code = 0;
   dwx_graph *replica_graph = nullptr;
   // the sample trace is one sampler's (include/dwx.h): per-rank traces of shards or replicas are not written
+  // (--diagnostics and --trace_pairs need --trace, parse_cmdline sees to that: they are refused here with it)
   if (args.trace) {
     std::cerr << "dw: --trace is not supported with --gpus or -c (n_datacopy): run a single rank" << std::endl;
     return 2;

@@ -2672,6 +2672,95 @@ int dwx_trace_diagnostics(dwx_sampler *s, uint32_t max_lag, double rhat_threshol
   return DWX_OK;
 }
 
+int dwx_trace_cooccurrence(dwx_sampler *s, const uint64_t *rows_a, const uint64_t *rows_b, uint64_t n_pairs,
+                           uint64_t first_entry, uint64_t n_entries, uint64_t *n_ab, uint64_t *n_a, uint64_t *n_b) {
+  if (!s) return fail(DWX_E_INVALID, "null sampler");
+  if (!s->d_trace) return fail(DWX_E_INVALID, "the sample trace was never enabled (dwx_trace_enable)");
+  if (n_pairs > 0xFFFFFFFFull) return fail(DWX_E_LIMIT, "the co-occurrence counts take at most 2^32 - 1 pairs a call");
+  if (n_entries > 0x7FFFFFFFull || s->trace_cap > 0x7FFFFFFFu)
+    return fail(DWX_E_LIMIT, "the co-occurrence counts take at most 2^31 - 1 entries, of a ring of at most 2^31 - 1");
+  if (first_entry > s->trace_count || n_entries > s->trace_count - first_entry)
+    return fail(DWX_E_INVALID, "entries outside the sample trace (dwx_trace_info: count)");
+  if (!n_pairs) return DWX_OK;
+  if (!rows_a || !rows_b || !n_ab) return fail(DWX_E_INVALID, "null argument");
+  const CompiledGraph &c = *s->cg;
+  const bool bit = s->trace_bits == 1;
+  // reference row -> (device position, dense value), once per call: the variable by a search in the rows' bases
+  // (the inverse of the translation dwx_trace_diagnostics returns its rows with), its position from CompiledGraph::pos
+  std::vector<uint32_t> pos[2];
+  std::vector<unsigned char> val[2];
+  RawArray<unsigned long long> counts;   // (staged: an error leaves the caller's arrays as they were)
+  // (ghost variables have no rows in the reference numbering -- graph_compile.cc: rows_of -- so every row < R is an owned
+  // variable's and what would be a ghost's row is out of range; the position check below is a guard, not an error case)
+  std::atomic<int> bad{0};               // 1: a row out of range, 2: the guard
+  int rc = guarded([&]() {
+    for (int side = 0; side < 2; ++side) {
+      const uint64_t *rows = side ? rows_b : rows_a;
+      pos[side].resize(n_pairs);
+      if (!bit) val[side].resize(n_pairs);
+      const uint64_t *first = c.ref_var_val_base.data();
+      parallel_ranges(n_pairs, host_threads(), [&](uint64_t ib, uint64_t ie) {
+        for (uint64_t i = ib; i < ie; ++i) {
+          if (rows[i] >= c.R) { bad = 1; return; }
+          const uint64_t v = (uint64_t)(std::upper_bound(first, first + c.V, rows[i]) - first) - 1;   // base[v] <= row < base[v + 1]
+          const uint32_t p = c.pos[v];
+          if (p >= c.Vo) { bad = 2; return; }
+          pos[side][i] = p;
+          if (!bit) val[side][i] = (c.v_meta[p] & VM_CATEGORICAL) ? (unsigned char)(rows[i] - first[v]) : (unsigned char)1;
+        }
+      });
+    }
+    if (n_entries) counts.reset(3 * n_pairs);
+  });
+  if (rc != DWX_OK) return rc;
+  if (bad == 1) return fail(DWX_E_INVALID, "value row out of range (dwx_graph_info: num_values)");
+  if (bad) return fail(DWX_E_INVALID, "ghost variables are not traced");
+  auto zero = [&](uint64_t *out) { if (out) std::fill(out, out + n_pairs, (uint64_t)0); };
+  if (!n_entries) { zero(n_ab); zero(n_a); zero(n_b); return DWX_OK; }
+  bool nomem = false;
+  rc = guarded([&]() {
+    rt::set_device(s->device);
+    void *d_pos[2] = {nullptr, nullptr}, *d_val[2] = {nullptr, nullptr}, *d_out = nullptr;
+    auto release = [&]() { for (int k = 0; k < 2; ++k) { rt::dfree(d_pos[k]); rt::dfree(d_val[k]); } rt::dfree(d_out); };
+    try {
+      d_out = optional_dmalloc(3 * n_pairs * 8);
+      for (int k = 0; k < 2; ++k) {
+        d_pos[k] = optional_dmalloc(n_pairs * 4);
+        if (!bit) d_val[k] = optional_dmalloc(n_pairs);
+      }
+      if (!d_out || !d_pos[0] || !d_pos[1] || (!bit && (!d_val[0] || !d_val[1]))) {
+        nomem = true;
+        release();
+        return;
+      }
+      for (int k = 0; k < 2; ++k) {
+        rt::h2d(d_pos[k], pos[k].data(), n_pairs * 4, s->stream);
+        if (!bit) rt::h2d(d_val[k], val[k].data(), n_pairs, s->stream);
+      }
+      const uint32_t slot0 = (uint32_t)((s->trace_next + s->trace_cap - s->trace_count + first_entry) % s->trace_cap);
+      const unsigned grid = (unsigned)std::min<uint64_t>((n_pairs + BLOCK_THREADS - 1) / BLOCK_THREADS, COOC_MAX_BLOCKS);
+      auto go = [&](auto kernel) {
+        rt::launch(kernel, grid, BLOCK_THREADS, 0, s->stream, (const unsigned long long *)s->d_trace, s->trace_words,
+                   s->trace_cap, slot0, (uint32_t)n_entries, (const uint32_t *)d_pos[0], (const uint32_t *)d_pos[1],
+                   (const unsigned char *)d_val[0], (const unsigned char *)d_val[1], n_pairs, (unsigned long long *)d_out);
+      };
+      if (bit) go(trace_cooc_kernel<1>); else go(trace_cooc_kernel<8>);
+      rt::d2h(counts.data(), d_out, 3 * n_pairs * 8, s->stream);
+      rt::stream_sync(s->stream);
+    } catch (...) {
+      release();
+      throw;
+    }
+    release();
+  });
+  if (rc != DWX_OK) return rc;
+  if (nomem) return fail(DWX_E_NOMEM, "no device memory for the co-occurrence counts' temporary arrays (up to 34 bytes per pair)");
+  uint64_t *outs[3] = {n_ab, n_a, n_b};
+  for (int k = 0; k < 3; ++k)
+    if (outs[k]) std::copy(counts.data() + k * n_pairs, counts.data() + (k + 1) * n_pairs, outs[k]);
+  return DWX_OK;
+}
+
 int dwx_get_tallies(dwx_sampler *s, uint64_t *tallies, uint64_t *nsamples) {
   if (!s) return fail(DWX_E_INVALID, "null sampler");
   return guarded([&]() {

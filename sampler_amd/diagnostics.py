@@ -10,6 +10,9 @@ For every value row of a whole graph (one chain) the same two numbers are comput
 where it lies: GibbsSampler.trace_diagnostics (include/dwx.h: dwx_trace_diagnostics), which equals split_rhat / ess
 of x[1, draws, rows] here with the rows' 0 / 1 indicator series.
 
+cooccurrence_stats turns the integer joint counts of GibbsSampler.trace_cooccurrence (include/dwx.h:
+dwx_trace_cooccurrence) into P(a and b), P(a), P(b) and the phi coefficient of each pair of value rows.
+
 Formulas: Gelman, Carlin, Stern, Dunson, Vehtari, Rubin, "Bayesian Data Analysis", 3rd ed., section 11.4-11.5.
 """
 import numpy as np
@@ -84,3 +87,22 @@ def ess(x):
         tau = 1.0 + 2.0 * (s - rho(0) if t else 0.0)
         out[j] = m * n / tau
     return out
+
+
+def cooccurrence_stats(n_ab, n_a, n_b, n):
+    """Counts of GibbsSampler.trace_cooccurrence -> (p_ab, p_a, p_b, phi), float64[n_pairs] each:
+    p_ab = n_ab / n, p_a = n_a / n, p_b = n_b / n, and the phi coefficient of the pair's 2 x 2 table,
+    phi = (n * n_ab - n_a * n_b) / sqrt(n_a * (n - n_a) * n_b * (n - n_b)) (Pearson's correlation of the two
+    indicator series).  phi is nan where a marginal is 0 or 1 (a series that never changed correlates with
+    nothing); with n == 0 all four are nan.  No warning either way."""
+    n_ab, n_a, n_b = (np.asarray(x).astype(np.float64) for x in (n_ab, n_a, n_b))
+    if n_ab.shape != n_a.shape or n_ab.shape != n_b.shape:
+        raise ValueError("n_ab, n_a and n_b: arrays of equal shape")
+    n = float(n)
+    if not n > 0.0:
+        nan = np.full(n_ab.shape, np.nan)
+        return nan, nan.copy(), nan.copy(), nan.copy()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = n_a * (n - n_a) * n_b * (n - n_b)
+        phi = np.where(den > 0.0, (n * n_ab - n_a * n_b) / np.sqrt(den), np.nan)
+    return n_ab / n, n_a / n, n_b / n, phi

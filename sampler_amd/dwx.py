@@ -29,7 +29,7 @@ SYMBOLS = [
     "dwx_sgd_apply_async", "dwx_sgd_finish",
     "dwx_get_weights", "dwx_set_weights", "dwx_average_weights_async",
     "dwx_clear_tallies", "dwx_get_tallies", "dwx_rb_enable", "dwx_get_rb_sums",
-    "dwx_trace_enable", "dwx_trace_info", "dwx_trace_read", "dwx_trace_diagnostics",
+    "dwx_trace_enable", "dwx_trace_info", "dwx_trace_read", "dwx_trace_diagnostics", "dwx_trace_cooccurrence",
     "dwx_get_assignments", "dwx_set_assignments", "dwx_get_sweep", "dwx_set_sweep",
     "dwx_device_buffer", "dwx_halo_create", "dwx_halo_destroy", "dwx_halo_buffer", "dwx_halo_message_bytes", "dwx_halo_pack_async",
     "dwx_halo_unpack_async", "dwx_stream", "dwx_kernel_time", "dwx_kernel_time_reset",
@@ -133,6 +133,7 @@ class Library:
         L.dwx_trace_info.argtypes = [vp, vp, vp, vp]
         L.dwx_trace_read.argtypes = [vp, u64, u64, vp, u64, vp]
         L.dwx_trace_diagnostics.argtypes = [vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
+        L.dwx_trace_cooccurrence.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp, vp]
         L.dwx_get_assignments.argtypes = [vp, i32, vp]
         L.dwx_set_assignments.argtypes = [vp, i32, vp]
         L.dwx_get_sweep.argtypes = [vp, vp]; L.dwx_set_sweep.argtypes = [vp, u64]
@@ -435,6 +436,27 @@ class GibbsSampler:
             self.h, int(max_lag), float(rhat_threshold), rhat.ctypes.data if arrays else None,
             ess.ctypes.data if arrays else None, flags.ctypes.data if arrays else None, C.addressof(summ)))
         return rhat, ess, flags, {name: getattr(summ, name) for name, _ in TraceDiagSummary._fields_}
+
+    def trace_cooccurrence(self, rows_a, rows_b, first=0, last=None):
+        """Joint counts of pairs of value rows over the trace's entries [first, last) (0 = oldest; default: all
+        held), counted on the device (include/dwx.h: dwx_trace_cooccurrence).  rows_a, rows_b: value rows in the
+        reference numbering as `tallies()`, pair i = (rows_a[i], rows_b[i]).
+        -> (uint64[n_pairs] n_ab, uint64[n_pairs] n_a, uint64[n_pairs] n_b, n): the entries where both rows'
+        indicators are 1, where each one's is, and the number of entries counted over
+        (diagnostics.cooccurrence_stats turns them into P(a and b), P(a), P(b), phi)."""
+        rows_a = np.ascontiguousarray(rows_a, np.uint64)
+        rows_b = np.ascontiguousarray(rows_b, np.uint64)
+        if rows_a.ndim != 1 or rows_a.shape != rows_b.shape:
+            raise ValueError("rows_a and rows_b: two one-dimensional arrays of equal length")
+        first = int(first)
+        n = (self.trace_info()[0] if last is None else int(last)) - first
+        if first < 0 or n < 0:
+            raise ValueError("entries [first, last): 0 <= first <= last")
+        n_ab, n_a, n_b = (np.zeros(len(rows_a), np.uint64) for _ in range(3))
+        # (a range outside the entries held, a row beyond num_values are the library's errors to report)
+        self.lib.check(self.lib.L.dwx_trace_cooccurrence(self.h, rows_a.ctypes.data, rows_b.ctypes.data, len(rows_a),
+                                                         first, n, n_ab.ctypes.data, n_a.ctypes.data, n_b.ctypes.data))
+        return n_ab, n_a, n_b, n
 
     def assignments(self, chain):
         out = np.zeros(self.V, np.uint64)

@@ -86,15 +86,17 @@ pull_grad_kernel(const uint32_t *inc_wid, const uint32_t *inc_slot, const float 
 // Block pull: the same sums as pull_grad_kernel without its random L2 gathers and with no
 // atomics at all.  The owners of the incidence entries are cut into blocks of <= BP_TILES
 // consecutive tiles whose ballot pairs (128 KiB) fit LDS; ell holds, per block and weight,
-// BP_ROW * DEPTH entries (host: build_level; what does not fit a row goes through
-// pull_grad_kernel).  Workgroup (block b, part p) copies b's ballots into LDS once, then
+// BP_ROW * DEPTH entries (host: build_level; what does not fit a row stays on the list for
+// fold_partials_kernel).  Workgroup (block b, part p) copies b's ballots into LDS once, then
 // streams its share of b's rows -- coalesced 16-byte loads, independent iterations, no
 // barrier -- and stores one partial sum per weight; fold_partials_kernel adds the blocks'
 // partials into grad.  Integer sums: the result equals pull_grad_kernel's.
 
 // UNIFORM: every record delta of the graph is the same (one feature value, one factor
 // function -- the usual case): its step comes in as an argument instead of an LDS table.
-template <int DEPTH, bool UNIFORM>
+// PACKED (with UNIFORM; the builders' form of such tables): a row is DEPTH planes of 8-byte words of three
+// 19-bit slots and a count (device_types.h: bp_pack_entry) -- 8 bytes per three entries instead of 16 per four.
+template <int DEPTH, bool UNIFORM, bool PACKED = false>
 __global__ void __launch_bounds__(BP_THREADS)
 pull_ell_kernel(const U32x4 *__restrict__ ell, const uint32_t *block_tile0, uint32_t parts, const long long *qtab,
                 uint32_t n_deltas, uint32_t Wp, const unsigned long long *delta, long long *__restrict__ partial) {
@@ -124,6 +126,39 @@ pull_ell_kernel(const U32x4 *__restrict__ ell, const uint32_t *block_tile0, uint
   // BP_UNROLL groups per step: all their row loads are issued before the first is used (the
   // compiler does not hoist them over the stores on its own); past the end the last group is
   // loaded again and not stored
+  if constexpr (PACKED) {
+    static_assert(UNIFORM, "packed rows carry no delta index");
+    const unsigned long long *__restrict__ rows8 = (const unsigned long long *)ell + (size_t)b * DEPTH * Wp;
+    for (uint32_t g = g0; g < g1; g += BP_UNROLL) {
+      unsigned long long row[BP_UNROLL][DEPTH];
+#pragma unroll
+      for (uint32_t u = 0; u < BP_UNROLL; ++u) {
+        const uint32_t w = umin(g + u, g1 - 1) * BP_THREADS + tid;
+#pragma unroll
+        for (int dd = 0; dd < DEPTH; ++dd) row[u][dd] = DWX_NT_LOAD(&rows8[(size_t)dd * Wp + w]);
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < BP_UNROLL; ++u) {
+        int cnt = 0;   // (at most BP_PK_ROW * DEPTH entries: a byte)
+#pragma unroll
+        for (int dd = 0; dd < DEPTH; ++dd) {
+          const unsigned long long e = row[u][dd];
+          const uint32_t n = (uint32_t)(e >> BP_PK_COUNT_SHIFT) & 3u;
+#pragma unroll
+          for (uint32_t k = 0; k < BP_PK_ROW; ++k) {
+            // branch-free, as below: an unused slot reads the bits of slot 0 and adds zero
+            const uint32_t slot = (uint32_t)(e >> (BP_SLOT_BITS * k)) & BP_SLOT_MASK;
+            const uint32_t word = (slot >> 6) * 4u + ((slot >> 5) & 1u);
+            const uint32_t nzw = s_words[word], ngw = s_words[word + 2u];
+            const uint32_t nz = (nzw >> (slot & 31u)) & (k < n ? 1u : 0u), ng = (ngw >> (slot & 31u)) & 1u;
+            cnt += nz ? (ng ? -1 : 1) : 0;
+          }
+        }
+        if (g + u < g1) DWX_NT_STORE((signed char)cnt, &out8[(g + u) * BP_THREADS + tid]);
+      }
+    }
+    return;
+  }
   for (uint32_t g = g0; g < g1; g += BP_UNROLL) {
     U32x4 row[BP_UNROLL][DEPTH];
 #pragma unroll
@@ -165,23 +200,74 @@ pull_ell_kernel(const U32x4 *__restrict__ ell, const uint32_t *block_tile0, uint
   }
 }
 
-// grad[w] += sum over blocks of partial[block][w]  (UNIFORM: byte counts of the one step q0)
+// grad[w] += sum over blocks of partial[block][w]  (UNIFORM: byte counts of the one step q0), plus the
+// entries that did not fit the blocks' rows: they stay on the weight-sorted list, weight w's at
+// [ov_start[w], ov_start[w + 1]) of inc_slot / inc_d (ov_start == nullptr: none), and the lane that owns
+// the weight adds them -- the owner's bits from the global ballot planes, the same step as
+// pull_grad_kernel -- so no atomic and no launch of its own is spent on them.  A lane owns FOLD_W
+// consecutive weights: the byte partials come as one 32-bit load per block, the lane's leftovers are
+// one contiguous stretch of the list, walked FOLD_W entries at a time with their gathers in flight together.
+// Integer sums: the result equals pull_grad_kernel's.
 template <bool UNIFORM>
 __global__ void __launch_bounds__(BLOCK_THREADS)
 fold_partials_kernel(const long long *partial, uint32_t n_blocks, uint32_t Wp, uint32_t W, long long *grad,
-                     const long long *qtab) {
-  const uint32_t stride = gridDim.x * blockDim.x;
+                     const long long *qtab, const uint32_t *ov_start, const uint32_t *inc_slot, const float *inc_d,
+                     const unsigned long long *delta) {
+  static_assert(FOLD_W == 4, "the byte partials of a lane's weights are one 32-bit word");
+  const uint32_t stride = gridDim.x * blockDim.x * FOLD_W;
   const long long q0 = qtab[0];
-  for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < W; w += stride) {
-    long long acc = 0;
+  for (uint32_t w0 = (blockIdx.x * blockDim.x + threadIdx.x) * FOLD_W; w0 < W; w0 += stride) {
+    long long acc[FOLD_W];
     if (UNIFORM) {
-      int cnt = 0;
-      for (uint32_t b = 0; b < n_blocks; ++b) cnt += ((const signed char *)partial)[(size_t)b * Wp + w];
-      acc = (long long)cnt * q0;
+      int cnt[FOLD_W] = {0, 0, 0, 0};
+      for (uint32_t b = 0; b < n_blocks; ++b) {   // (w0 + 3 < Wp, a multiple of BP_THREADS: the word is inside the row)
+        const uint32_t x = *(const uint32_t *)((const signed char *)partial + (size_t)b * Wp + w0);
+#pragma unroll
+        for (uint32_t j = 0; j < FOLD_W; ++j) cnt[j] += (int)(signed char)(x >> (8u * j));
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < FOLD_W; ++j) acc[j] = (long long)cnt[j] * q0;
     } else {
-      for (uint32_t b = 0; b < n_blocks; ++b) acc += partial[(size_t)b * Wp + w];
+#pragma unroll
+      for (uint32_t j = 0; j < FOLD_W; ++j) acc[j] = 0;
+      for (uint32_t b = 0; b < n_blocks; ++b) {
+#pragma unroll
+        for (uint32_t j = 0; j < FOLD_W; ++j) acc[j] += partial[(size_t)b * Wp + w0 + j];
+      }
     }
-    if (acc) grad[w] += acc;
+    if (ov_start) {
+      uint32_t at[FOLD_W + 1];   // (ov_start has W + 1 entries; weights past W own nothing)
+#pragma unroll
+      for (uint32_t j = 0; j <= FOLD_W; ++j) at[j] = ov_start[umin(w0 + j, W)];
+      for (uint32_t i0 = at[0]; i0 < at[FOLD_W]; i0 += FOLD_W) {
+        uint32_t slot[FOLD_W];
+        float dd[FOLD_W];
+        DeltaPair dp[FOLD_W];
+#pragma unroll
+        for (uint32_t k = 0; k < FOLD_W; ++k) {
+          const uint32_t i = umin(i0 + k, at[FOLD_W] - 1);
+          slot[k] = inc_slot[i];
+          dd[k] = UNIFORM ? 0.0f : inc_d[i];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < FOLD_W; ++k) dp[k] = ((const DeltaPair *)delta)[slot[k] >> 6];
+#pragma unroll
+        for (uint32_t k = 0; k < FOLD_W; ++k) {
+          const uint32_t i = i0 + k;
+          const unsigned long long bit = 1ull << (slot[k] & 63u);
+          long long v = 0;
+          if (i < at[FOLD_W] && (dp[k].nz & bit)) {
+            const long long q = UNIFORM ? q0 : llrint(FIX_SCALE * (double)dd[k]);
+            v = (dp[k].ng & bit) ? -q : q;
+          }
+#pragma unroll
+          for (uint32_t j = 0; j < FOLD_W; ++j) acc[j] += (i >= at[j] && i < at[j + 1]) ? v : 0;
+        }
+      }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < FOLD_W; ++j)
+      if (w0 + j < W && acc[j]) grad[w0 + j] += acc[j];
   }
 }
 

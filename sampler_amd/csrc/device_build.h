@@ -45,7 +45,7 @@ void build_static_tables(const TileDesc *d_tiles, uint32_t n_tiles, const uint32
 // incidence list of every (SGD-triggering boolean variable, non-fixed record with a non-zero delta)
 // pair of the pull tiles, sorted by (group, weight), and -- graphs with >= block_pull_min_w weights and
 // few distinct deltas -- per group the block-pull table (rows of BP_ROW x depth entries per (variable
-// block, weight)), with what did not fit a row left on the list.  Bit for bit the host builder's
+// block, weight)), with what did not fit a row left on the list and the per-weight starts of those leftovers.  Bit for bit the host builder's
 // structures.  h_tile_info[tile] = group | mode << 30 (1: all records, 2: pre-signed ones only),
 // 0xFFFFFFFF: none.  The device buffers of the result belong to the caller (hipFree / rt::dfree).
 struct Incidence {
@@ -55,8 +55,9 @@ struct Incidence {
   float *d_inc_d = nullptr;
   struct BlockTable {
     U32x4 *d_ell = nullptr;
+    uint32_t *d_ov_start = nullptr;              // [W + 1]: where each weight's leftovers start in the group's list
     std::vector<uint32_t> tile0;
-    uint32_t blocks = 0, depth = 0;
+    uint32_t blocks = 0, depth = 0;              // depth: 16-byte rows of 4 entries, or (one delta) 8-byte planes of 3
     uint64_t total = 0, on_list = 0;             // the group's entries; those left on the list
   };
   std::vector<BlockTable> bp;                    // [groups], or empty: no block pull

@@ -365,11 +365,11 @@ template <bool FILL>
 __global__ void __launch_bounds__(256)
 ell_walk_kernel(const unsigned long long *vals, uint64_t g0, const uint32_t *w_at, uint32_t W, const uint32_t *block_of,
                 const uint32_t *tile0, uint32_t depth, uint64_t Wp, const uint32_t *dvals, uint32_t n_dvals, U32x4 *ell,
-                uint32_t *ov, const uint32_t *ovs, const unsigned long long *keys, unsigned long long *kept_keys,
+                uint32_t packed, uint32_t *ov, const uint32_t *ovs, const unsigned long long *keys, unsigned long long *kept_keys,
                 unsigned long long *kept_vals, uint64_t kept_base) {
   const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= W) return;
-  const uint32_t cap = BP_ROW * depth;
+  const uint32_t cap = (packed ? BP_PK_ROW : BP_ROW) * depth;
   uint32_t cur = 0xFFFFFFFFu, kk = 0, o = 0;
   const uint64_t out0 = FILL ? 0 : kept_base + ovs[w];
   for (uint64_t i = g0 + w_at[w]; i < g0 + w_at[w + 1]; ++i) {
@@ -377,7 +377,10 @@ ell_walk_kernel(const unsigned long long *vals, uint64_t g0, const uint32_t *w_a
     const uint32_t slot = (uint32_t)(v >> 32), ti = slot / BLOCK_THREADS, vb = block_of[ti];
     if (vb != cur) { cur = vb; kk = 0; }
     if (kk < cap) {
-      if (FILL) {
+      if (FILL && packed) {      // (the lane owns its weight's words: plain read-modify-write; the host zeroed them)
+        unsigned long long *word = (unsigned long long *)ell + ((uint64_t)vb * depth + kk / BP_PK_ROW) * Wp + w;
+        *word = bp_pack_entry(*word, kk % BP_PK_ROW, (ti - tile0[vb]) * BLOCK_THREADS + slot % BLOCK_THREADS);
+      } else if (FILL) {
         const uint32_t bits = (uint32_t)v;
         uint32_t a = 0, b = n_dvals;
         while (a < b) { const uint32_t mid = (a + b) >> 1; if (dvals[mid] < bits) a = mid + 1; else b = mid; }
@@ -576,6 +579,7 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
   auto dalloc = [&](size_t bytes) { void *p = scratch_take(bytes); scratch.push_back(p); return p; };
   auto release = [&]() { for (void *p : scratch) scratch_give(p); scratch.clear(); };
   U32x4 *ell_now = nullptr;
+  uint32_t *ovs_now = nullptr;
   // DWX_TIMING=1: wall time of the steps on stderr (each ends on a stream sync)
   const bool timing = getenv("DWX_TIMING") != nullptr;
   auto t_step = std::chrono::steady_clock::now();
@@ -663,6 +667,8 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
       std::vector<uint32_t> block_of(n_tiles, 0), tile0_all;
       std::vector<uint64_t> tile0_off(n_groups + 1, 0);
       std::vector<uint32_t> depth(n_groups, 0);
+      const bool packed = dvals.size() == 1;      // one delta: three 19-bit slots per 8-byte word, zero = no entry
+      const size_t row_bytes = packed ? 8 : sizeof(U32x4);
       for (uint32_t k = 0; k < n_groups; ++k) {
         tile0_off[k] = tile0_all.size();
         if (!kept_n[k]) continue;
@@ -675,7 +681,7 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
         const uint64_t nvb = tile0_all.size() - first;
         const double lambda = (double)kept_n[k] / ((double)W * (double)nvb);
         if (lambda < 0.5) { tile0_all.resize(first); continue; }      // nearly empty rows: this group keeps its list
-        depth[k] = lambda > 3.2 ? 2u : 1u;
+        depth[k] = bp_row_depth(lambda, packed);
       }
       tile0_off[n_groups] = tile0_all.size();
       uint32_t *d_block_of = (uint32_t *)dalloc((size_t)n_tiles * 4), *d_tile0 = (uint32_t *)dalloc(tile0_all.size() * 4 + 4);
@@ -688,17 +694,18 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
       DEVB_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, d_ov, d_ovs, 0u, (size_t)W, rocprim::plus<uint32_t>(), st));
       void *scan_tmp = dalloc(scan_bytes);
       out.bp.resize(n_groups);
+      std::vector<uint32_t> ov_total(n_groups, 0);      // (sources of asynchronous copies: alive until the sync below)
       const unsigned wgrid = (W + 256) / 256;
       for (uint32_t k = 0; k < n_groups; ++k) {
         const uint64_t nvb = tile0_off[k + 1] - tile0_off[k];
         if (!depth[k] || !nvb) continue;
         const uint64_t g0 = c_start[k], g1 = c_start[k + 1];
         hipLaunchKernelGGL(weight_start_kernel, dim3(wgrid), dim3(256), 0, st, keys, g0, g1, k, W, d_wat);
-        DEVB_HIP(output_malloc((void **)&ell_now, nvb * depth[k] * Wp * sizeof(U32x4)));
-        DEVB_HIP(hipMemsetAsync(ell_now, 0xFF, nvb * depth[k] * Wp * sizeof(U32x4), st));
+        DEVB_HIP(output_malloc((void **)&ell_now, nvb * depth[k] * Wp * row_bytes));
+        DEVB_HIP(hipMemsetAsync(ell_now, packed ? 0 : 0xFF, nvb * depth[k] * Wp * row_bytes, st));
         hipLaunchKernelGGL(ell_walk_kernel<true>, dim3(wgrid), dim3(256), 0, st, vals, g0, (const uint32_t *)d_wat, W,
                            (const uint32_t *)d_block_of, (const uint32_t *)(d_tile0 + tile0_off[k]), depth[k], Wp,
-                           (const uint32_t *)d_dvals, (uint32_t)dvals.size(), ell_now, d_ov, (const uint32_t *)nullptr, keys,
+                           (const uint32_t *)d_dvals, (uint32_t)dvals.size(), ell_now, (uint32_t)packed, d_ov, (const uint32_t *)nullptr, keys,
                            (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint64_t)0);
         DEVB_HIP(hipGetLastError());
         DEVB_HIP(rocprim::exclusive_scan(scan_tmp, scan_bytes, d_ov, d_ovs, 0u, (size_t)W, rocprim::plus<uint32_t>(), st));
@@ -707,20 +714,27 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
         DEVB_HIP(hipMemcpyAsync(&last_ovs, d_ovs + (W - 1), 4, hipMemcpyDeviceToHost, st));
         DEVB_HIP(hipStreamSynchronize(st));
         kept_n[k] = (uint64_t)last_ov + last_ovs;
+        // the leftovers' per-weight starts stay with the table: d_ovs's W offsets and the total
+        ov_total[k] = (uint32_t)kept_n[k];
+        DEVB_HIP(output_malloc((void **)&ovs_now, ((size_t)W + 1) * 4));
+        DEVB_HIP(hipMemcpyAsync(ovs_now, d_ovs, (size_t)W * 4, hipMemcpyDeviceToDevice, st));
+        DEVB_HIP(hipMemcpyAsync(ovs_now + W, &ov_total[k], 4, hipMemcpyHostToDevice, st));
         if (kept_n[k])
           hipLaunchKernelGGL(ell_walk_kernel<false>, dim3(wgrid), dim3(256), 0, st, vals, g0, (const uint32_t *)d_wat, W,
                              (const uint32_t *)d_block_of, (const uint32_t *)(d_tile0 + tile0_off[k]), depth[k], Wp,
-                             (const uint32_t *)d_dvals, (uint32_t)dvals.size(), (U32x4 *)nullptr, (uint32_t *)nullptr,
+                             (const uint32_t *)d_dvals, (uint32_t)dvals.size(), (U32x4 *)nullptr, (uint32_t)packed, (uint32_t *)nullptr,
                              (const uint32_t *)d_ovs, keys, kk, kv, g0);
         DEVB_HIP(hipGetLastError());
         Incidence::BlockTable &bt = out.bp[k];
         bt.d_ell = ell_now; ell_now = nullptr;
+        bt.d_ov_start = ovs_now; ovs_now = nullptr;
         bt.tile0.assign(tile0_all.begin() + tile0_off[k], tile0_all.begin() + tile0_off[k + 1]);
         bt.blocks = (uint32_t)nvb; bt.depth = depth[k];
         bt.total = g1 - g0; bt.on_list = kept_n[k];
         max_blocks = std::max(max_blocks, nvb);
       }
       if (!max_blocks) out.bp.clear();
+      DEVB_HIP(hipStreamSynchronize(st));               // (ov_total dies with this scope)
     }
     step("block tables");
     // groups without a table keep all their entries: the kept arrays hold them at the same positions
@@ -755,8 +769,8 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
     step("list columns");
   } catch (...) {
     release();
-    (void)hipFree(ell_now);
-    for (auto &bt : out.bp) (void)hipFree(bt.d_ell);
+    (void)hipFree(ell_now); (void)hipFree(ovs_now);
+    for (auto &bt : out.bp) { (void)hipFree(bt.d_ell); (void)hipFree(bt.d_ov_start); }
     (void)hipFree(out.d_inc_wid); (void)hipFree(out.d_inc_slot); (void)hipFree(out.d_inc_d);
     out = Incidence();
     throw;

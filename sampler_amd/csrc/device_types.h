@@ -220,6 +220,26 @@ constexpr uint32_t BP_UNROLL = DWX_BP_UNROLL;     // weight groups in flight per
 constexpr uint32_t BP_SLOT_BITS = 19, BP_SLOT_MASK = (1u << BP_SLOT_BITS) - 1;
 constexpr uint32_t BP_EMPTY = 0xFFFFFFFFu;
 constexpr uint32_t BP_DELTA_SLOTS = 4096, BP_MAX_DELTAS = BP_DELTA_SLOTS - 1;   // (the last slot stays 0: BP_EMPTY decodes to it)
+// Tables with ONE record delta (pull_ell_kernel<.., UNIFORM, PACKED>) need no delta index: a row is `depth`
+// planes of 8-byte words with BP_PK_ROW 19-bit slots each, slot k in bits 19 k .. 19 k + 18, filled from
+// slot 0 up, and in bits 57-58 how many of them hold an entry -- so every one of the 2^19 slot codes stays a
+// real variable (0x7FFFF is the last lane of a full block) and an unused slot reads as slot 0, not counted.
+constexpr uint32_t BP_PK_ROW = 3, BP_PK_COUNT_SHIFT = 57, BP_PK_MAX_DEPTH = 4;
+constexpr unsigned long long bp_pack_entry(unsigned long long word, uint32_t k, uint32_t code) {
+  return (word & ~(3ull << BP_PK_COUNT_SHIFT)) | ((unsigned long long)code << (BP_SLOT_BITS * k)) |
+         ((unsigned long long)(k + 1u) << BP_PK_COUNT_SHIFT);
+}
+// Rows per (block, weight) from lambda = the group's entries / (weights x blocks); what a row cannot take
+// stays on the list for fold_partials_kernel's lane of the weight.  32-bit rows: 4 or 8 entries.  Packed rows:
+// 3, 6, 9 or 12 -- the fewest planes that leave no more than about 9 % of the entries of a Poisson(lambda)
+// row over (3 entries: lambda <= 1.8, 6: <= 4.8, 9: <= 7.8).  A plane costs 8 bytes per row, a leftover entry
+// 4 bytes and one L2 gather: at those limits the next plane would hold 0.15 to 0.5 entries per row.  Config 3,
+// lambda = 5: 9 entries in 24 bytes, 1.1 % left over; 12 entries would read a third more bytes for that 1 %.
+constexpr uint32_t bp_row_depth(double lambda, bool packed) {
+  if (!packed) return lambda > 3.2 ? 2u : 1u;
+  return lambda > 7.8 ? 4u : lambda > 4.8 ? 3u : lambda > 1.8 ? 2u : 1u;
+}
+constexpr uint32_t FOLD_W = 4;                    // consecutive weights per lane of fold_partials_kernel
 // one block of ballot pairs + the table of deltas: exactly the 160 KiB of a CU
 constexpr uint32_t BP_LDS_BYTES = BP_TILES * 64 + BP_DELTA_SLOTS * 8;
 // sweep8_kernel<MULTI>: a run of at least this many sweeps over a tile with idle lanes is cut

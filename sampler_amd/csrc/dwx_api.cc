@@ -252,10 +252,12 @@ struct dwx_sampler {
     double c_max = 0.0, t_max = 0.0;   // largest h and largest static T of any (chunk, weight)
     // block pull (pull_ell_kernel; graphs with many weights): per group of the tables (the
     // un-split sweep, or each chunk of a split one) entry rows per (variable block, weight);
-    // d_inc_* then only holds what did not fit a row.  blocks == 0: the group pulls its list.
+    // d_inc_* then only holds what did not fit a row, and d_ov_start where each weight's leftovers
+    // start in the group's part of it (W + 1 offsets from inc_begin: fold_partials_kernel's lane of
+    // the weight sums them).  blocks == 0: the group pulls its list with pull_grad_kernel.
     struct BlockTable {
       U32x4 *d_ell = nullptr;
-      uint32_t *d_tile0 = nullptr;
+      uint32_t *d_tile0 = nullptr, *d_ov_start = nullptr;
       uint32_t blocks = 0, depth = 0, parts = 0;
     };
     std::vector<BlockTable> bp;           // [groups] or empty
@@ -279,7 +281,7 @@ struct dwx_sampler {
       rt::graph_exec_destroy(gexec);
       rt::dfree(d_supers); rt::dfree(d_sorted); rt::dfree(d_chunk_tiles);
       rt::dfree(d_inc_wid); rt::dfree(d_inc_slot); rt::dfree(d_inc_d); rt::dfree(d_t_static);
-      for (auto &t : bp) { rt::dfree(t.d_ell); rt::dfree(t.d_tile0); }
+      for (auto &t : bp) { rt::dfree(t.d_ell); rt::dfree(t.d_tile0); rt::dfree(t.d_ov_start); }
       rt::dfree(d_bp_qtab); rt::dfree(d_bp_partial);
     }
   };
@@ -1015,12 +1017,15 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
           if (!inc.bp[k].blocks) continue;
           dwx_sampler::Level::BlockTable &bt = L->bp[k];
           bt.d_ell = inc.bp[k].d_ell;
+          bt.d_ov_start = inc.bp[k].d_ov_start;
           bt.d_tile0 = upload(inc.bp[k].tile0, s->stream);
           bt.blocks = inc.bp[k].blocks; bt.depth = inc.bp[k].depth;
           bt.parts = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rt::cu_count() / bt.blocks, inc.wp / BP_THREADS));
           if (bp_timing)
-            fprintf(stderr, "[dwx block pull] group %u: %u blocks x depth %u, %zu deltas, %llu of %llu entries on the list (device build)\n",
-                    k, bt.blocks, bt.depth, inc.dvals.size(), (unsigned long long)inc.bp[k].on_list, (unsigned long long)inc.bp[k].total);
+            fprintf(stderr, "[dwx block pull] group %u: %u blocks x depth %u (%u entries, %llu bytes of rows), %zu deltas, %llu of %llu entries on the list (device build)\n",
+                    k, bt.blocks, bt.depth, bt.depth * (inc.dvals.size() == 1 ? BP_PK_ROW : BP_ROW),
+                    (unsigned long long)((uint64_t)bt.blocks * bt.depth * inc.wp * (inc.dvals.size() == 1 ? 8 : 16)), inc.dvals.size(),
+                    (unsigned long long)inc.bp[k].on_list, (unsigned long long)inc.bp[k].total);
         }
         std::vector<long long> qtab(inc.dvals.size());
         for (size_t i = 0; i < inc.dvals.size(); ++i) {
@@ -1032,8 +1037,10 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
         L->bp_deltas = (uint32_t)inc.dvals.size(); L->bp_wp = (uint32_t)inc.wp;
         rt::allow_dynamic_lds(pull_ell_kernel<1, false>, BP_LDS_BYTES);
         rt::allow_dynamic_lds(pull_ell_kernel<2, false>, BP_LDS_BYTES);
-        rt::allow_dynamic_lds(pull_ell_kernel<1, true>, BP_LDS_BYTES);
-        rt::allow_dynamic_lds(pull_ell_kernel<2, true>, BP_LDS_BYTES);
+        rt::allow_dynamic_lds(pull_ell_kernel<1, true, true>, BP_LDS_BYTES);
+        rt::allow_dynamic_lds(pull_ell_kernel<2, true, true>, BP_LDS_BYTES);
+        rt::allow_dynamic_lds(pull_ell_kernel<3, true, true>, BP_LDS_BYTES);
+        rt::allow_dynamic_lds(pull_ell_kernel<4, true, true>, BP_LDS_BYTES);
       }
       rt::stream_sync(s->stream);
     } else {
@@ -1143,7 +1150,8 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
           const uint64_t nvb = tile0.size();
           const double lambda = (double)n / ((double)c.W * (double)nvb);
           if (lambda < 0.5) continue;   // nearly empty rows: this group keeps its list
-          const uint32_t depth = lambda > 3.2 ? 2u : 1u, cap = BP_ROW * depth;
+          const bool packed = dvals.size() == 1;       // one delta: three 19-bit slots per 8-byte word
+          const uint32_t depth = bp_row_depth(lambda, packed), cap = (packed ? BP_PK_ROW : BP_ROW) * depth;
           // (2) where each weight's entries start inside the group (they are sorted by weight)
           std::vector<uint64_t> w_at(c.W + 1, n);
           parallel_ranges(n, nth, [&](uint64_t b, uint64_t e) {
@@ -1153,8 +1161,9 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
             }
           });
           // (3) the table; entries of one weight come in tile order: blocks ascending
-          RawArray<U32x4> ell(nvb * depth * Wp);
-          parallel_ranges(ell.size(), nth, [&](uint64_t b, uint64_t e) { std::memset((void *)(ell.data() + b), 0xFF, (e - b) * sizeof(U32x4)); });
+          RawArray<unsigned long long> ell8(nvb * depth * Wp * (packed ? 1 : 2));   // (8-byte words: U32x4 rows are two)
+          U32x4 *ell = (U32x4 *)ell8.data();
+          parallel_ranges(ell8.size(), nth, [&](uint64_t b, uint64_t e) { std::memset((void *)(ell8.data() + b), packed ? 0 : 0xFF, (e - b) * 8); });
           std::vector<uint64_t> &ovs = ov_start[k];
           ovs.assign(c.W + 1, 0);
           parallel_ranges(c.W, nth, [&](uint64_t wb, uint64_t we) {
@@ -1165,7 +1174,10 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
                 const Inc &r = ent[i];
                 const uint32_t ti = r.slot / BLOCK_THREADS, vb = block_of[ti];
                 if (vb != cur) { cur = vb; kk = 0; }
-                if (kk < cap) {
+                if (kk < cap && packed) {
+                  unsigned long long &word = ell8[((uint64_t)vb * depth + kk / BP_PK_ROW) * Wp + w];
+                  word = bp_pack_entry(word, kk % BP_PK_ROW, (ti - tile0[vb]) * BLOCK_THREADS + r.slot % BLOCK_THREADS);
+                } else if (kk < cap) {
                   uint32_t bits; std::memcpy(&bits, &r.d, 4);
                   const uint32_t di = (uint32_t)(std::lower_bound(dvals.begin(), dvals.end(), bits) - dvals.begin());
                   ell[((uint64_t)vb * depth + kk / BP_ROW) * Wp + w].v[kk % BP_ROW] =
@@ -1198,16 +1210,18 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
             });
           }
           dwx_sampler::Level::BlockTable &bt = L->bp[k];
-          bt.d_ell = upload_raw(ell.data(), ell.size(), s->stream);
+          bt.d_ell = (U32x4 *)upload_raw(ell8.data(), ell8.size(), s->stream);
           bt.d_tile0 = upload(tile0, s->stream);
+          std::vector<uint32_t> ovs32(ovs.begin(), ovs.end());   // (< 2^32: the whole list is)
+          bt.d_ov_start = upload(ovs32, s->stream);
           bt.blocks = (uint32_t)nvb; bt.depth = depth;
           // parts per block: one workgroup per CU over all blocks (it owns the CU's whole LDS)
           bt.parts = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rt::cu_count() / nvb, Wp / BP_THREADS));
           max_blocks = std::max(max_blocks, nvb);
           rt::stream_sync(s->stream);   // ell dies with this scope
           if (bp_timing)
-            fprintf(stderr, "[dwx block pull] group %u: %llu blocks x depth %u, %zu deltas, %llu of %llu entries on the list\n",
-                    k, (unsigned long long)nvb, depth, dvals.size(), (unsigned long long)ov_count[k], (unsigned long long)n);
+            fprintf(stderr, "[dwx block pull] group %u: %llu blocks x depth %u (%u entries, %llu bytes of rows), %zu deltas, %llu of %llu entries on the list\n",
+                    k, (unsigned long long)nvb, depth, cap, (unsigned long long)(ell8.size() * 8), dvals.size(), (unsigned long long)ov_count[k], (unsigned long long)n);
         }
         if (max_blocks) {
           // the lists shrink to what the tables left (same order: by weight inside a group)
@@ -1232,8 +1246,10 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
           L->bp_deltas = (uint32_t)dvals.size(); L->bp_wp = (uint32_t)Wp;
           rt::allow_dynamic_lds(pull_ell_kernel<1, false>, BP_LDS_BYTES);
           rt::allow_dynamic_lds(pull_ell_kernel<2, false>, BP_LDS_BYTES);
-          rt::allow_dynamic_lds(pull_ell_kernel<1, true>, BP_LDS_BYTES);
-          rt::allow_dynamic_lds(pull_ell_kernel<2, true>, BP_LDS_BYTES);
+          rt::allow_dynamic_lds(pull_ell_kernel<1, true, true>, BP_LDS_BYTES);
+          rt::allow_dynamic_lds(pull_ell_kernel<2, true, true>, BP_LDS_BYTES);
+          rt::allow_dynamic_lds(pull_ell_kernel<3, true, true>, BP_LDS_BYTES);
+          rt::allow_dynamic_lds(pull_ell_kernel<4, true, true>, BP_LDS_BYTES);
           rt::stream_sync(s->stream);
           by_w.clear(); by_c.clear();
           src = &kept;
@@ -1548,9 +1564,8 @@ void enqueue_learn_chunk(dwx_sampler *s, uint32_t chunk) {
   }
   // block pull of the same group as the list: the whole sweep (un-split, after the last colour
   // launch) or this chunk; what did not fit the block tables' rows stays on the weight-sorted list
-  // (config 3: 2.8 % of the entries) for pull_grad_kernel.  (The list walked on a side stream
-  // beside pull_ell_kernel, fold_partials_kernel waiting for both: bench step 0.5523 -> 0.5507 ms,
-  // pull 0.1127 -> 0.1108 -- inside the noise, not kept.)
+  // (config 3: 3.7 % of the entries) and is summed by fold_partials_kernel's lane of the weight.
+  // A group without a table pulls its whole list with pull_grad_kernel.
   const dwx_sampler::Level::BlockTable *bt = nullptr;
   if (fast && !L.bp.empty() && (split || chunk + 1 == s->plan_chunks.size())) {
     bt = &L.bp[split ? chunk : 0];
@@ -1577,20 +1592,34 @@ void enqueue_learn_chunk(dwx_sampler *s, uint32_t chunk) {
                  (const uint32_t *)bt->d_tile0, bt->parts, (const long long *)L.d_bp_qtab, L.bp_deltas, L.bp_wp,
                  (const unsigned long long *)s->d_delta, L.d_bp_partial);
     };
-    const bool uni = L.bp_deltas == 1;
-    if (bt->depth == 2) { if (uni) go(pull_ell_kernel<2, true>); else go(pull_ell_kernel<2, false>); }
-    else { if (uni) go(pull_ell_kernel<1, true>); else go(pull_ell_kernel<1, false>); }
+    const bool uni = L.bp_deltas == 1;   // one delta: packed rows of 1 to 4 planes; else 32-bit entries, 1 or 2 rows
+    if (uni) {
+      switch (bt->depth) {
+        case 1: go(pull_ell_kernel<1, true, true>); break;
+        case 2: go(pull_ell_kernel<2, true, true>); break;
+        case 3: go(pull_ell_kernel<3, true, true>); break;
+        default: go(pull_ell_kernel<4, true, true>); break;
+      }
+    } else if (bt->depth == 2) {
+      go(pull_ell_kernel<2, false>);
+    } else {
+      go(pull_ell_kernel<1, false>);
+    }
     const uint32_t W = (uint32_t)s->cg->W;
-    const unsigned fgrid = std::min<unsigned>((W + BLOCK_THREADS - 1) / BLOCK_THREADS, 4096u);
+    const unsigned fgrid = std::min<unsigned>((W + BLOCK_THREADS * FOLD_W - 1) / (BLOCK_THREADS * FOLD_W), 4096u);
+    const uint32_t *ov = pe > pb ? (const uint32_t *)bt->d_ov_start : nullptr;   // (nothing left over: no list to walk)
     if (uni)
       rt::launch(fold_partials_kernel<true>, fgrid, BLOCK_THREADS, 0, s->stream, (const long long *)L.d_bp_partial,
-                 bt->blocks, L.bp_wp, W, s->d_grad, (const long long *)L.d_bp_qtab);
+                 bt->blocks, L.bp_wp, W, s->d_grad, (const long long *)L.d_bp_qtab, ov, (const uint32_t *)(L.d_inc_slot + pb),
+                 (const float *)(L.d_inc_d + pb), (const unsigned long long *)s->d_delta);
     else
       rt::launch(fold_partials_kernel<false>, fgrid, BLOCK_THREADS, 0, s->stream, (const long long *)L.d_bp_partial,
-                 bt->blocks, L.bp_wp, W, s->d_grad, (const long long *)L.d_bp_qtab);
+                 bt->blocks, L.bp_wp, W, s->d_grad, (const long long *)L.d_bp_qtab, ov, (const uint32_t *)(L.d_inc_slot + pb),
+                 (const float *)(L.d_inc_d + pb), (const unsigned long long *)s->d_delta);
     pulled = true;
+  } else if (pe > pb) {
+    launch_list(s->stream);
   }
-  if (pe > pb) launch_list(s->stream);
   span_end(s, sp, launches, pulled, chunk == 0, 1, true);
 }
 

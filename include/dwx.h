@@ -33,7 +33,7 @@ extern "C" {
 enum {
   DWX_OK = 0,
   DWX_E_INVALID = -1,  /* malformed graph / argument (reference: assert/abort)   */
-  DWX_E_LIMIT = -2,    /* graph exceeds the compact 32-bit layout               */
+  DWX_E_LIMIT = -2,    /* graph exceeds the compact 32-bit layout / a numeric domain */
   DWX_E_DEVICE = -3,   /* HIP error or no device                                */
   DWX_E_NOMEM = -4
 };
@@ -57,7 +57,8 @@ typedef struct dwx_graph_desc {
   const uint64_t *fac_edge_offset; /* [num_factors+1]                             */
   const uint64_t *fac_weight_id;
   const double *fac_feature_value; /* finite; |value| <= 65536 on a learnable weight (DWX_E_LIMIT
-                                      beyond: gradients are summed in 2^-30 fixed point, int64);
+                                      beyond: gradients are summed in 2^-30 fixed point, int64 --
+                                      and the sums of one mini-batch must fit: dwx_sgd_plan);
                                       |value| below ~5e-10 contributes no gradient            */
   const uint64_t *edge_vid;
   const uint64_t *edge_equal_to;   /* equalPredicate as in the file               */
@@ -259,7 +260,13 @@ int dwx_wait(dwx_sampler *s);
  * nothing ride along with a neighbour); with batches == 1 the update is applied once after
  * the last chunk, otherwise after every chunk.
  *   dwx_sgd_plan -> n_chunks;  for c in chunks: dwx_sgd_accumulate_async(c) [+ collective,
- *   + dwx_sgd_apply_async where due];  dwx_sgd_finish. */
+ *   + dwx_sgd_apply_async where due];  dwx_sgd_finish.
+ * DWX_E_LIMIT (dwx_sgd_plan and dwx_sample_sgd_async, before anything is sampled; state untouched, no plan
+ * left): a mini-batch of the plan could take a weight's int64 sums -- gradient 2^30 x sum t |g|, update count,
+ * curvature bound 2^10 x sum kappa d S -- past 2^63 - 1 in the worst case over all assignments (DESIGN.md 4,
+ * "Learning domain"; 65 536 visits of a +-1 factor with feature value 65 536 on one weight).  The text names
+ * the weight.  A finer plan (force_batches, a smaller step_cap) whose mini-batches fit is accepted.  Sums a
+ * driver all-reduces over ranks are the driver's to bound. */
 int dwx_sgd_plan(dwx_sampler *s, double stepsize, uint32_t force_batches, uint32_t *batches,
                  uint32_t *n_chunks, double *effective_stepsize);
 /* The curvature estimate R(batches) dwx_sgd_plan works with (cached per batch count).  A

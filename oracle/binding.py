@@ -69,6 +69,9 @@ def lib():
         L.orc_sched_apply.argtypes = [vp, dbl]
         L.orc_sched_apply_h.argtypes = [vp, dbl, vp]
         L.orc_sched_curvature.argtypes = [vp, vp, vp]
+        for n in ("orc_sched_sample_sgd", "orc_sched_accumulate", "orc_sched_apply", "orc_sched_apply_h",
+                  "orc_sched_curvature"):
+            getattr(L, n).restype = i32
         L.orc_grad.restype = vp; L.orc_grad.argtypes = [vp]
         L.orc_set_var_id_offset.argtypes = [vp, u64]
         L.orc_set_sampling_weight_f32.argtypes = [vp, i32]
@@ -203,6 +206,11 @@ class Oracle:
         self._sched_keep = (order, launch_off, s)
         return s
 
+    def _range(self, rc):
+        """the learning calls fail when a sum leaves int64, the device's container (never a silent wrap)"""
+        if rc != 0:
+            raise OverflowError("oracle: " + self.L.orc_last_error().decode())
+
     def sched_check_independent(self, order, launch_off):
         s = self._sched(order, launch_off)
         return bool(self.L.orc_sched_check_independent(self.h, C.addressof(s)))
@@ -215,26 +223,26 @@ class Oracle:
     def sched_sample_sgd(self, order, launch_off, seed, sweep, stepsize):
         self.L.orc_set_sampling_weight_f32(self.h, 1)
         s = self._sched(order, launch_off)
-        self.L.orc_sched_sample_sgd(self.h, C.addressof(s), seed, sweep, stepsize)
+        self._range(self.L.orc_sched_sample_sgd(self.h, C.addressof(s), seed, sweep, stepsize))
 
     def sched_accumulate(self, order, launch_off, seed, sweep):
         self.L.orc_set_sampling_weight_f32(self.h, 1)
         s = self._sched(order, launch_off)
-        self.L.orc_sched_accumulate(self.h, C.addressof(s), seed, sweep)
+        self._range(self.L.orc_sched_accumulate(self.h, C.addressof(s), seed, sweep))
 
     def sched_apply(self, stepsize, hess=None):
         """hess: int64[W] curvature bounds to use instead of the accumulated ones."""
         if hess is None:
-            self.L.orc_sched_apply(self.h, stepsize)
+            self._range(self.L.orc_sched_apply(self.h, stepsize))
         else:
             hess = np.ascontiguousarray(hess, np.int64)
-            self.L.orc_sched_apply_h(self.h, stepsize, hess.ctypes.data)
+            self._range(self.L.orc_sched_apply_h(self.h, stepsize, hess.ctypes.data))
 
     def sched_curvature(self, order):
         order = np.ascontiguousarray(order, np.uint64)
         s = self._sched(order, np.array([0, len(order)], np.uint64))
         out = np.zeros(self.W, np.int64)
-        self.L.orc_sched_curvature(self.h, C.addressof(s), out.ctypes.data)
+        self._range(self.L.orc_sched_curvature(self.h, C.addressof(s), out.ctypes.data))
         return out
 
     @property

@@ -115,6 +115,11 @@ struct orc_sampler {
   std::vector<uint64_t> c_var_val_base, c_value_sparse, c_index_base, c_index_len, c_assign_dense;
   // schedule-mode accumulators
   std::vector<int64_t> GT;   // G[W], T[W], then H[W] (curvature bounds, schedule mode)
+  // the same sums in 128 bits: the device's containers are int64, and an oracle that wrapped with them
+  // would agree with a wrapped device bit for bit.  GT holds their image while every sum fits; a sum
+  // that leaves int64 makes orc_sched_accumulate / orc_sched_apply fail (range_fault) instead.
+  std::vector<__int128> GT128;
+  bool range_fault = false;
   uint64_t vid_offset = 0;
   std::vector<uint8_t> fixed_mask;  // schedule mode: variables whose potentials the device sums in fixed point
   bool f32w = false;  // schedule mode: potentials use the weight rounded to f32 (device's sampling copy)
@@ -717,10 +722,31 @@ extern "C" void orc_sched_sample(orc_sampler *s, const orc_schedule *sch, uint64
   }
 }
 
-extern "C" void orc_sched_accumulate(orc_sampler *s, const orc_schedule *sch, uint64_t seed,
-                                     uint64_t sweep) {
+namespace {
+// GT := GT128 where it fits; -> 0, or -1 with the text in orc_last_error (sticky until the next apply)
+int publish_sums(orc_sampler *s) {
+  const __int128 lo = INT64_MIN, hi = INT64_MAX;
+  for (uint64_t i = 0; i < 3 * s->W; ++i) {
+    const __int128 v = s->GT128[i];
+    if (v < lo || v > hi) {
+      if (!s->range_fault)
+        g_err = std::string(i < s->W ? "gradient sum" : (i < 2 * s->W ? "update count" : "curvature bound")) +
+                " of weight " + std::to_string(i % s->W) + " leaves int64 (about " + std::to_string((double)v) + ")";
+      s->range_fault = true;
+      s->GT[i] = v < lo ? INT64_MIN : INT64_MAX;
+    } else {
+      s->GT[i] = (int64_t)v;
+    }
+  }
+  return s->range_fault ? -1 : 0;
+}
+}  // namespace
+
+extern "C" int orc_sched_accumulate(orc_sampler *s, const orc_schedule *sch, uint64_t seed,
+                                    uint64_t sweep) {
   std::vector<double> buf;
-  int64_t *G = s->GT.data(), *T = s->GT.data() + s->W, *H = s->GT.data() + 2 * s->W;
+  if (s->GT128.size() != 3 * s->W) s->GT128.assign(3 * s->W, 0);
+  __int128 *G = s->GT128.data(), *T = s->GT128.data() + s->W, *H = s->GT128.data() + 2 * s->W;
   for (uint64_t i = 0; i < sch->n_order; ++i) {
     uint64_t vid = sch->order[i];
     double A, B;
@@ -736,6 +762,7 @@ extern "C" void orc_sched_accumulate(orc_sampler *s, const orc_schedule *sch, ui
     });
     s->curvature_bounds(vid, [H](uint64_t wid, double bound) { H[wid] += llrint(kHessScale * bound); });
   }
+  return publish_sums(s);
 }
 
 // The device's batched update (apply_kernel, sampler_amd/csrc/sweep_kernels.h): the end point
@@ -747,16 +774,27 @@ extern "C" void orc_sched_accumulate(orc_sampler *s, const orc_schedule *sch, ui
 // zero, integrated piece by piece (l1_flow below restates apply_kernel's).
 // hess != null: use these bounds instead of the accumulated ones (the device's fallback for
 // plans without per-chunk tables applies every chunk with the WHOLE sweep's bounds)
-extern "C" void orc_sched_apply_h(orc_sampler *s, double stepsize, const int64_t *hess);
-extern "C" void orc_sched_apply(orc_sampler *s, double stepsize) { orc_sched_apply_h(s, stepsize, nullptr); }
+extern "C" int orc_sched_apply_h(orc_sampler *s, double stepsize, const int64_t *hess);
+extern "C" int orc_sched_apply(orc_sampler *s, double stepsize) { return orc_sched_apply_h(s, stepsize, nullptr); }
 // out[W] = the curvature bounds of the SGD-triggering variables of the schedule (fixed point)
-extern "C" void orc_sched_curvature(orc_sampler *s, const orc_schedule *sch, int64_t *out) {
-  for (uint64_t w = 0; w < s->W; ++w) out[w] = 0;
+extern "C" int orc_sched_curvature(orc_sampler *s, const orc_schedule *sch, int64_t *out) {
+  std::vector<__int128> acc(s->W, 0);
   for (uint64_t i = 0; i < sch->n_order; ++i) {
     const uint64_t vid = sch->order[i];
     if (!s->sgd_triggers(s->vars[vid])) continue;
-    s->curvature_bounds(vid, [out](uint64_t wid, double bound) { out[wid] += llrint(kHessScale * bound); });
+    s->curvature_bounds(vid, [&acc](uint64_t wid, double bound) { acc[wid] += llrint(kHessScale * bound); });
   }
+  int rc = 0;
+  for (uint64_t w = 0; w < s->W; ++w) {
+    if (acc[w] > (__int128)INT64_MAX) {
+      g_err = "curvature bound of weight " + std::to_string(w) + " leaves int64";
+      out[w] = INT64_MAX;
+      rc = -1;
+    } else {
+      out[w] = (int64_t)acc[w];
+    }
+  }
+  return rc;
 }
 namespace {
 constexpr double kCurvMid = 0.5;   // DWX_CURV_MID of aux_kernels.h
@@ -810,8 +848,16 @@ double l1_update(double w0, double G, double h, double T, double stepsize, doubl
   return kCurvMid * h * stepsize <= 0.0625 ? l1_visits(w0, G, T, stepsize, reg) : l1_flow(w0, G, h, T, stepsize, reg);
 }
 }  // namespace
-extern "C" void orc_sched_apply_h(orc_sampler *s, double stepsize, const int64_t *hess) {
+extern "C" int orc_sched_apply_h(orc_sampler *s, double stepsize, const int64_t *hess) {
   int64_t *G = s->GT.data(), *T = s->GT.data() + s->W, *H = s->GT.data() + 2 * s->W;
+  // a sum that left int64 has no image in the device's containers: nothing is applied, the sums are dropped
+  const bool fault = s->range_fault;
+  s->range_fault = false;
+  s->GT128.assign(3 * s->W, 0);
+  if (fault) {
+    for (uint64_t i = 0; i < 3 * s->W; ++i) s->GT[i] = 0;
+    return -1;
+  }
   // batch_step of aux_kernels.h: the flow with the middle of [0, h] as curvature, capped at 1 / (h + r)
   auto step = [stepsize](double h, double r) {
     const double c = kCurvMid * h + r, cb = h + r;
@@ -831,10 +877,11 @@ extern "C" void orc_sched_apply_h(orc_sampler *s, double stepsize, const int64_t
     }
     s->weight_values[w] = x;
   }
+  return 0;
 }
 
-extern "C" void orc_sched_sample_sgd(orc_sampler *s, const orc_schedule *sch, uint64_t seed,
-                                     uint64_t sweep, double stepsize) {
-  orc_sched_accumulate(s, sch, seed, sweep);
-  orc_sched_apply(s, stepsize);
+extern "C" int orc_sched_sample_sgd(orc_sampler *s, const orc_schedule *sch, uint64_t seed,
+                                    uint64_t sweep, double stepsize) {
+  const int rc = orc_sched_accumulate(s, sch, seed, sweep);
+  return orc_sched_apply(s, stepsize) ? -1 : rc;
 }

@@ -44,6 +44,10 @@ int fail(int code, const std::string &msg) {
   return code;
 }
 
+struct RangeError : std::runtime_error {   // -> DWX_E_LIMIT
+  using std::runtime_error::runtime_error;
+};
+
 template <class Fn>
 int guarded(Fn &&fn) {
   try {
@@ -51,6 +55,8 @@ int guarded(Fn &&fn) {
     return DWX_OK;
   } catch (const std::bad_alloc &) {
     return fail(DWX_E_NOMEM, "out of host memory");
+  } catch (const RangeError &e) {
+    return fail(DWX_E_LIMIT, e.what());
   } catch (const std::invalid_argument &e) {
     return fail(DWX_E_INVALID, e.what());
   } catch (const std::exception &e) {
@@ -250,6 +256,9 @@ struct dwx_sampler {
     long long *d_t_static = nullptr;   // [rows][T[W] | h[W]]: static update counts, curvature bounds
     uint32_t rows = 0;
     double c_max = 0.0, t_max = 0.0;   // largest h and largest static T of any (chunk, weight)
+    // not empty: a mini-batch of this level can take a weight's int64 sums past 2^63 - 1
+    // (learning_range_error); the level holds its chunks only and no plan may use it
+    std::string range_error;
     // block pull (pull_ell_kernel; graphs with many weights): per group of the tables (the
     // un-split sweep, or each chunk of a split one) entry rows per (variable block, weight);
     // d_inc_* then only holds what did not fit a row, and d_ov_start where each weight's leftovers
@@ -854,6 +863,114 @@ void ensure_level_layout(dwx_sampler *s, dwx_sampler::Level *L, uint32_t batches
   L->d_supers = d_supers;
 }
 
+// The domain of the learning sums.  A mini-batch adds, per weight, int64 sums in
+// fixed point: G += llrint(2^30 t g) and T += llrint(2^30 t) per visited record (DWX_BUF_GRAD), and the
+// static h = sum llrint(2^10 kappa d S) (for_each_record_bound).  Nothing on the sweep path saturates or
+// checks them -- a wrapped sum is a gradient of the wrong sign, and the oracle's schedule mode, which
+// restates the same containers, used to agree with it bit for bit -- so the domain is enforced here,
+// where a plan's mini-batches are made.  Per group of variables that share an update (`groups`:
+// device-order position ranges) and per weight, the WORST case of each sum over any assignment:
+//   G: a record's |g| = |pot_free - pot_evid| is at most its delta (record_delta: the two signs of a
+//      unary factor, 2 |f| (arity - 1) beyond); its visits carry a truthiness of 1 in all, or -- a
+//      categorical variable under noise_aware -- of at most the variable's total truthiness (row d is
+//      visited with t_d as the evidence row and with every other value's t as the proposal's row: up to one
+//      visit per value row, each rounding its own term, so one unit per value row is added on top);
+//   T: the same visits, 2^30 t each;   h: exactly the table's value.
+// Every term is rounded UP to an integer, so the true sum of every prefix, in any order, stays inside
+// the bound: the kernels' partial sums (LDS accumulators, block rows, per-record atomics) cannot wrap
+// either.  Sums in uint64, saturating: a bound of exactly 2^63 - 1 passes, 2^63 does not.
+// -> empty, or the text of the DWX_E_LIMIT error, naming the weight.
+std::string learning_range_error(dwx_sampler *s, const std::vector<std::pair<uint32_t, uint32_t>> &groups) {
+  const CompiledGraph &c = *s->cg;
+  const dwx_options &o = s->opts;
+  if (!c.W || groups.empty()) return std::string();
+  constexpr uint64_t kLimit = (uint64_t)INT64_MAX, kSat = UINT64_MAX;
+  const uint32_t nth = host_threads();
+  std::vector<uint64_t> acc(3 * c.W, 0);   // [G | T | h] bounds of the current group
+  auto sat_add = [](uint64_t *a, uint64_t v) -> uint64_t {   // -> the value before
+    uint64_t old = __atomic_load_n(a, __ATOMIC_RELAXED);
+    for (;;) {
+      const uint64_t next = old > kSat - v ? kSat : old + v;
+      if (__atomic_compare_exchange_n(a, &old, next, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) return old;
+    }
+  };
+  auto up = [](double x) -> uint64_t {   // ceil, saturating
+    return x >= 18446744073709549568.0 ? kSat : (uint64_t)std::ceil(x);
+  };
+  for (size_t k = 0; k < groups.size(); ++k) {
+    const uint32_t p0 = groups[k].first, p1 = groups[k].second;
+    const uint32_t T = std::max(1u, std::min<uint32_t>(nth, (p1 - p0) / 4096u + 1u));
+    std::vector<std::vector<uint32_t>> touched(T);
+    parallel_parts(p1 - p0, T, [&](uint32_t t, uint64_t b, uint64_t e) {
+      // a thread's adds go through a small direct-mapped cache: heavily tied weights (eight weights
+      // on 10^7 records) would otherwise be one contended cache line
+      struct Slot { uint32_t wid; uint64_t g, t, h; };
+      constexpr uint32_t kSlots = 64;
+      Slot cache[kSlots];
+      for (auto &sl : cache) sl = Slot{0xFFFFFFFFu, 0, 0, 0};
+      auto flush = [&](Slot &sl) {
+        if (sl.wid == 0xFFFFFFFFu) return;
+        const uint64_t before = sat_add(&acc[c.W + sl.wid], sl.t);
+        sat_add(&acc[sl.wid], sl.g);
+        sat_add(&acc[2 * c.W + sl.wid], sl.h);
+        if (before == 0) touched[t].push_back(sl.wid);
+        sl = Slot{0xFFFFFFFFu, 0, 0, 0};
+      };
+      auto slot_of = [&](uint32_t wid) -> Slot & {
+        Slot &sl = cache[wid % kSlots];
+        if (sl.wid != wid) { flush(sl); sl.wid = wid; }
+        return sl;
+      };
+      auto add = [](uint64_t &a, uint64_t v) { a = a > kSat - v ? kSat : a + v; };
+      for (uint32_t p = p0 + (uint32_t)b; p < p0 + (uint32_t)e; ++p) {
+        const uint32_t m = c.v_meta[p];
+        if (!triggers_sgd(o, m)) continue;
+        const bool cat = m & VM_CATEGORICAL;
+        double tt = 1.0;
+        if (cat && o.noise_aware) {
+          tt = 0.0;
+          if (!c.row_truth.empty())
+            for (uint32_t r = c.v_row[p]; r < c.v_row[p + 1]; ++r) tt += c.row_truth[r];
+        }
+        if (!(tt > 0.0)) continue;
+        // (such a record is visited up to once per value row, each visit rounding its own term: half a unit each)
+        const uint64_t visits_slack = cat && o.noise_aware ? c.v_row[p + 1] - c.v_row[p] : 0u;
+        const uint64_t t_up = up(FIX_SCALE * tt) + visits_slack;
+        for (uint32_t e2 = c.row_ptr[c.v_row[p]]; e2 < c.row_ptr[c.v_row[p + 1]]; ++e2) {
+          if (c.edges[e2].packed & EDGE_FIXED_FLAG) continue;
+          Slot &sl = slot_of(c.edges[e2].wid);
+          add(sl.t, t_up);
+          add(sl.g, up(FIX_SCALE * (tt * record_delta(c, e2, cat))));
+          add(sl.g, visits_slack);
+        }
+        for_each_record_bound(c, p, [&](uint32_t e2, double bound) {
+          add(slot_of(c.edges[e2].wid).h, up(H_SCALE * bound));
+        });
+      }
+      for (auto &sl : cache) flush(sl);
+    }, 4096);
+    uint32_t bad = 0xFFFFFFFFu;
+    for (const auto &list : touched)
+      for (uint32_t w : list)
+        if (acc[w] > kLimit || acc[c.W + w] > kLimit || acc[2 * c.W + w] > kLimit) bad = std::min(bad, w);
+    if (bad != 0xFFFFFFFFu) {
+      const uint64_t w = bad;
+      char buf[512];
+      const char *which = acc[bad] > kLimit ? "gradient sum (2^30 x sum of t |g|)"
+                          : (acc[2 * c.W + bad] > kLimit ? "curvature bound (2^10 x sum of kappa d S)" : "update count (2^30 x sum of t)");
+      const uint64_t v = acc[bad] > kLimit ? acc[bad] : (acc[2 * c.W + bad] > kLimit ? acc[2 * c.W + bad] : acc[c.W + bad]);
+      snprintf(buf, sizeof buf,
+               "the learning sums of weight %llu can leave int64 in mini-batch %zu of %zu: worst-case %s = %.17g%s, "
+               "the limit is 2^63 - 1 (fewer or smaller feature values on this weight, or a finer plan: dwx_sgd_plan's force_batches)",
+               (unsigned long long)w, k + 1, groups.size(), which, (double)v, v == kSat ? " or more" : "");
+      return buf;
+    }
+    for (const auto &list : touched)
+      for (uint32_t w : list) acc[w] = acc[c.W + w] = acc[2 * c.W + w] = 0;
+  }
+  return std::string();
+}
+
 // Everything a plan level needs to run its chunks without per-record atomics: per chunk,
 // (a) the static update counts of its boolean variables -- a boolean variable that triggers
 // SGD visits every factor of its row once with t = 1 (src/factor_graph.cc:265-273),
@@ -900,6 +1017,20 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
     lv_t0 = t;
   };
   lv_step("chunks");
+  {
+    // before any table is summed: the groups of variables that share an update (the un-split sweep:
+    // ONE, whatever its colour launches) must keep every weight's sums inside int64
+    std::vector<std::pair<uint32_t, uint32_t>> groups;
+    if (batches == 1) groups.push_back({c.tile_v.front(), c.tile_v.back()});
+    else for (const auto &ch : L->chunks) groups.push_back({c.tile_v[ch.t0], c.tile_v[ch.t1]});
+    L->range_error = learning_range_error(s, groups);
+    lv_step("range of the learning sums");
+    if (!L->range_error.empty()) {
+      dwx_sampler::Level *ret = L.get();
+      s->levels[batches] = std::move(L);
+      return ret;
+    }
+  }
   if (s->opts.plan_layouts == 1 || (s->opts.plan_layouts == 0 && devb::available() && !getenv("DWX_HOST_BUILD")))
     ensure_level_layout(s, L.get(), batches);
   lv_step("weight-sorted layout");
@@ -1496,6 +1627,22 @@ void make_plan(dwx_sampler *s, double stepsize, uint32_t force_batches) {
     for (uint32_t b = B / 2; b >= 2; b /= 2) {
       if (cap > 0) (void)row_sum_bound(s, b);
       (void)build_level(s, b);
+    }
+  }
+  // Nothing has been sampled yet: a plan whose mini-batches could wrap a weight's int64 sums is refused
+  // here (DWX_E_LIMIT; learning_range_error), and so is one that would borrow the curvature bounds of
+  // an un-split level that does not fit (plans without per-chunk tables apply with the whole sweep's).
+  {
+    dwx_sampler::Level *L = build_level(s, B);
+    const std::string *why = !L->range_error.empty() ? &L->range_error : nullptr;
+    if (!why && !L->fast) {
+      auto it = s->levels.find(1);
+      if (it != s->levels.end() && !it->second->range_error.empty()) why = &it->second->range_error;
+    }
+    if (why) {
+      s->plan_valid = false;
+      s->plan_level = nullptr;
+      throw RangeError(*why);
     }
   }
   s->plan_level = build_level(s, B);
@@ -2864,7 +3011,7 @@ int dwx_device_buffer(dwx_sampler *s, int which, void **dev_ptr, uint64_t *nbyte
     case DWX_BUF_TSTATIC: {
       auto it = s->levels.find(1);
       *dev_ptr = it == s->levels.end() ? nullptr : it->second->d_t_static;
-      *nbytes = c.W * 16;
+      *nbytes = *dev_ptr ? c.W * 16 : 0;   // (none: the un-split sweep is outside the learning domain)
       break;
     }
     case DWX_BUF_TSTATIC_PLAN:

@@ -297,6 +297,37 @@ def tied_goldens():
         json.dump(out, open(path, "w"), indent=1, sort_keys=True)
 
 
+RANDGRAPH_SEEDS = [0, 1]
+RANDGRAPH_FLAGS = {"short": []}
+RANDGRAPH_FLAGS.update(FLAG_GOLDENS)
+
+
+def randgraph_goldens():
+    """Two random mixed graphs (tests/randgraph.py: random_graph(seed, V=40, F=160, W=10) -- every factor function,
+    arities 1-4, sparse domains, duplicate variables inside a factor, duplicate factors), written by
+    sampler_amd.binary_format, with the reference's `dw gibbs -l 30 -i 50 -t 1 -c 1` output under the flag sets
+    short (none), l1, lne and l1_lne.  Pins the oracle's reference mode on general graphs
+    (tests/test_learning_range.py), which the exact learning model's comparisons lean on.  A few KB each."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from sampler_amd import binary_format
+    from randgraph import random_graph
+    base = ["-l", "30", "-i", "50", "--alpha", "0.01", "--diminish", "0.95", "--reg_param", "0.01", "-t", "1", "-c", "1"]
+    for seed in RANDGRAPH_SEEDS:
+        dst = os.path.join(HERE, "randgraph_s%d" % seed)
+        os.makedirs(dst, exist_ok=True)
+        binary_format.write_graph(random_graph(seed, V=40, F=160, W=10), dst)
+        for tag, extra in RANDGRAPH_FLAGS.items():
+            a = base + extra
+            with tempfile.TemporaryDirectory() as out:
+                run_ref(dst, a, out)
+                shutil.copy(os.path.join(out, "inference_result.out.weights.text"), os.path.join(dst, "ref_%s.weights.text" % tag))
+                shutil.copy(os.path.join(out, "inference_result.out.text"), os.path.join(dst, "ref_%s.text" % tag))
+            with open(os.path.join(dst, "ref_%s.args" % tag), "w") as f:
+                f.write(" ".join(a) + "\n")
+        print("golden: randgraph_s%d" % seed)
+
+
 def codec_goldens():
     """The reference's text2bin codec fixtures (test/text2bin/: TSV inputs and xxd dumps of
     the expected big-endian bytes) -- data files of the reference's tests."""
@@ -328,3 +359,5 @@ if __name__ == "__main__":
         synth_second_runs()
     if "tied" in which:
         tied_goldens()
+    if "randgraph" in which:
+        randgraph_goldens()

@@ -319,7 +319,7 @@ struct orc_sampler {
   }
 
   // ---- schedule mode only: curvature bound of a variable's SGD updates, per factor ----
-  // Restates the device's static table (sampler_amd/csrc/dwx_api.cc
+  // Restates the device's static table (sampler_amd/csrc/level_build.cc
   // for_each_record_bound): delta of a factor = how far it can move the variable's potential
   // between two of its values -- |sign(hit) - sign(miss)| |f| at arity 1 (the sign functions of
   // src/factor.h:112-299 with one satisfied bit), 2 |f| (arity - 1) beyond; a boolean variable

@@ -1,7 +1,7 @@
 // device_build.h -- see device_build.hip: heavy phases of the graph build as HIP kernels.  Plain
 // declarations over device pointers (no HIP types), so that dwx_api.cc calls them the same way in the
 // product (device_build.hip) and in the tests' host harness (tests/hipemu/device_build_stub.cc:
-// available() == false, the host builders run).
+// available() == false, the host builders of level_build.cc and graph_compile.cc run).
 #ifndef DWX_DEVICE_BUILD_H_
 #define DWX_DEVICE_BUILD_H_
 
@@ -32,7 +32,7 @@ void build_sorted_records(const TileDesc *d_tiles, const EdgeRec *d_edges, const
                           const SuperTile *d_supers, uint32_t n_supers, const uint32_t *h_dbits, uint32_t n_dbits,
                           uint64_t n_total, SortRec8 *d_out, void *stream);
 
-// A plan level's static tables (build_level (a) of dwx_api.cc): d_table[n_groups][T[W] | h[W]] --
+// A plan level's static tables (hostb::build_static_tables of level_build.cc on the host): d_table[n_groups][T[W] | h[W]] --
 // update counts of the boolean variables (fixed point 2^-30) and curvature bounds of all variables
 // (2^-10) of the tiles of every group (h_group_of[tile], host memory; 0xFFFFFFFF: no group) -- bit for
 // bit the host's; *t_max / *h_max: the largest entries.  Synchronises `stream`.
@@ -41,7 +41,7 @@ void build_static_tables(const TileDesc *d_tiles, uint32_t n_tiles, const uint32
                          const uint8_t *d_w_fixed, uint32_t W, uint32_t n_groups, bool learn_non_evidence, bool noise_aware,
                          long long *d_table, long long *t_max, long long *h_max, void *stream);
 
-// A plan level's pull-gradient structures (build_level (b) of dwx_api.cc), built on the device: the
+// A plan level's pull-gradient structures (hostb::build_incidence of level_build.cc), built on the device: the
 // incidence list of every (SGD-triggering boolean variable, non-fixed record with a non-zero delta)
 // pair of the pull tiles, sorted by (group, weight), and -- graphs with >= block_pull_min_w weights and
 // few distinct deltas -- per group the block-pull table (rows of BP_ROW x depth entries per (variable
@@ -70,7 +70,7 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
                      uint32_t bp_tiles, Incidence &out, void *stream);
 
 // max(power-iteration estimate, largest diagonal entry) of the curvature bound of the mini-batch of
-// variables [p0, p1) (row_sum_bound's dense branch in dwx_api.cc, WITHOUT its 1.1 safety factor): the
+// variables [p0, p1) (hostb::batch_curvature's dense branch in level_build.cc, WITHOUT row_sum_bound's 1.1 safety factor): the
 // host's arithmetic term for term, 64-bit fixed-point sums.  `sc`: scratch vectors kept between calls.
 struct CurvatureScratch {
   void *x = nullptr, *y = nullptr, *yfix = nullptr, *dfix = nullptr, *part = nullptr, *small = nullptr;

@@ -1,5 +1,5 @@
 // device_build.hip -- the heavy phases of the host-side graph build as HIP kernels (SURVEY.md 8 f1,
-// "optional GPU build"): what graph_compile.cc / dwx_api.cc do on the host's cores with counting
+// "optional GPU build"): what graph_compile.cc / level_build.cc do on the host's cores with counting
 // sorts and per-record walks, done on the device the sampler is created on, from the columns that
 // are uploaded anyway.  The host builders stay, as the checker (tests/test_gpu_parity.py compares
 // the buffers byte for byte) and for the sanitizer harness, whose link has a stub for this file.
@@ -7,11 +7,11 @@
 //   build_sorted_records   the weight-sorted second copy of the boolean all-unary tiles' records
 //                          (graph_compile.cc: build_sorted_layout's radix sorts per super-tile)
 //   build_static_tables    a plan level's static update counts T and curvature bounds h per chunk
-//                          (dwx_api.cc: build_level's walk over every SGD-triggering variable's records)
+//                          (level_build.cc: build_static_tables' walk over every SGD-triggering variable's records)
 //   batch_curvature        the curvature estimate of one mini-batch: three power steps on its Hessian bound
-//                          (dwx_api.cc: row_sum_bound)
+//                          (level_build.cc: batch_curvature)
 //   build_incidence        a plan level's pull-gradient incidence list, sorted by (chunk, weight), and its
-//                          block-pull tables (dwx_api.cc: build_level's two counting sorts + table fill)
+//                          block-pull tables (level_build.cc: build_incidence's two counting sorts + table fill)
 //
 // Sorting itself is rocPRIM's radix sort (a plain library sort, as the guide allows for plain
 // library operations); everything around it is written here.  Replaces nothing of the reference
@@ -169,7 +169,7 @@ compose_sorted_kernel(const unsigned long long *keys, const uint32_t *vals, uint
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
     out[i] = SortRec8{(uint32_t)keys[i], vals[i]};
 }
-// ---- static update counts T and curvature bounds h of a plan level (dwx_api.cc: build_level (a)) ----
+// ---- static update counts T and curvature bounds h of a plan level (level_build.cc: build_static_tables) ----
 // The host's record_delta / for_each_record_bound, restated: how far one record can move its
 // owner's potential between two of the owner's values (|sign(hit) - sign(miss)| |f| for a unary
 // factor, 2 |f| (arity - 1) beyond; 0 for a fixed weight), and the Gershgorin share
@@ -256,7 +256,7 @@ table_max_kernel(const long long *table, uint64_t n_groups, uint32_t W, unsigned
   }
   if ((threadIdx.x & 63u) == 0) { atomicMax(&out[0], mt); atomicMax(&out[1], mh); }
 }
-// ---- the pull gradient's incidence list and block-pull tables of a plan level (build_level (b)) ----
+// ---- the pull gradient's incidence list and block-pull tables of a plan level (level_build.cc: build_incidence) ----
 // tile_info[tile]: group | mode << 30 (mode 1: every record of the tile's triggering variables, 2: only
 // the pre-signed ones -- TILE_PULL_UNARY), 0xFFFFFFFF: the tile owns no entry.  An entry = (SGD-triggering
 // boolean variable, non-fixed record of its row with dd = hit - miss != 0): key = group << 32 | weight
@@ -412,7 +412,7 @@ incidence_columns_kernel(const unsigned long long *keys, const unsigned long lon
     id[dst0 + i] = d;
   }
 }
-// ---- curvature estimate of one mini-batch (dwx_api.cc: row_sum_bound, the dense branch) ----
+// ---- curvature estimate of one mini-batch (level_build.cc: batch_curvature, the dense branch) ----
 // Three power steps y = H x on the batch's curvature bound H = sum over its SGD-triggering variables of
 // kappa d d^T, from x = 1: per variable dot = sum d x[wid], then y[wid] += kappa d dot -- as 64-bit
 // FIXED-POINT atomic adds (scale = 2^62 / (R U): R the batch's records, U the largest possible term),

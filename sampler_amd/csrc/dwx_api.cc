@@ -22,6 +22,10 @@
 #include "device_build.h"
 #include "graph_compile.h"
 #include "host_parallel.h"
+#include "level_build.h"
+#if defined(DWX_EMU) && !defined(DWX_EMU_LEVEL_BUILD_UNIT)
+#include "level_build.cc"   // (a host harness recipe that does not compile that unit itself: the suite of a revision before it)
+#endif
 
 #include "sweep_kernels.h"   // (device_intrinsics.h: the HIP runtime shim rt_hip.h comes with it)
 #include "diag_kernels.h"    // (dwx_trace_diagnostics)
@@ -38,6 +42,10 @@ using namespace dwx;
 
 namespace {
 thread_local std::string g_err;
+
+// the heavy build phases run on the sampler's device where the library can (device_build.hip);
+// DWX_HOST_BUILD=1: the host builders, which are also their checker (level_build.cc, graph_compile.cc)
+bool build_on_device() { return devb::available() && !getenv("DWX_HOST_BUILD"); }
 
 int fail(int code, const std::string &msg) {
   g_err = msg;
@@ -722,102 +730,6 @@ void enqueue_inference(dwx_sampler *s) {
   ++s->sweep;
 }
 
-// Tile boundaries of colour launch l cut into at most nb runs of (nearly) equal SGD work
-// (records visited by sgd_on_variable; query variables sample but do not learn, so a cut
-// by tile count would put all the learning of an evidence-after-query launch in half of
-// the batches).  Returns strictly increasing boundaries from the launch's first tile to
-// its last.
-std::vector<uint32_t> cut_launch(const dwx_sampler *s, size_t l, uint32_t nb) {
-  const CompiledGraph &c = *s->cg;
-  const uint32_t t0 = c.launch_tile[l], t1 = c.launch_tile[l + 1];
-  std::vector<uint32_t> cut{t0};
-  if (t1 == t0) return cut;
-  const uint64_t w0 = s->sgd_work[t0], total = s->sgd_work[t1] - w0;
-  // nb pieces for the colour with the MOST work; a colour with less gets as many as keep its
-  // pieces no bigger than that colour's (a greedy colouring leaves most of the work in the first
-  // colours: cutting the small late colours nb-fold too only multiplies dependent launches --
-  // 20 colours x 64 batches x 6 kernels on the power-law test graph)
-  if (nb > 1 && s->sgd_work_max_launch > 0)
-    nb = (uint32_t)std::max<uint64_t>(1, (total * nb + s->sgd_work_max_launch - 1) / s->sgd_work_max_launch);
-  nb = std::max(1u, std::min(nb, t1 - t0));
-  for (uint32_t b = 1; b < nb; ++b) {
-    uint32_t t;
-    if (total == 0) {
-      t = t0 + (uint32_t)((uint64_t)(t1 - t0) * b / nb);
-    } else {
-      const uint64_t target = w0 + (total / nb) * b + (total % nb) * b / nb;
-      t = (uint32_t)(std::lower_bound(s->sgd_work.begin() + t0, s->sgd_work.begin() + t1, target) -
-                     s->sgd_work.begin());
-    }
-    if (t > cut.back() && t < t1) cut.push_back(t);
-  }
-  cut.push_back(t1);
-  return cut;
-}
-
-bool triggers_sgd(const dwx_options &o, uint32_t meta) {
-  return o.learn_non_evidence || (!o.noise_aware && (meta & VM_EVIDENCE)) ||
-         (o.noise_aware && (meta & VM_TRUTHINESS));
-}
-
-// How far one record can move its owner's potential between two of the owner's values, the
-// building block of every curvature bound below: |sign(hit) - sign(miss)| * |f| for a unary
-// factor (src/factor.h:112-299 at arity 1; boolean owner: hit = "1 satisfies the predicate",
-// miss = "0 does"; categorical owner: the record sits in the row of the value that satisfies
-// it), 2 |f| (arity - 1) for wider ones (a sign spans [-1, 1]; LINEAR counts up to arity - 1).
-// Fixed weights do not move: 0.  The oracle restates this (orc_sched_accumulate).
-double host_unary_sign(uint32_t func, bool sat) {
-  switch (func) {
-    case FUNC_AND: case FUNC_ISTRUE: case FUNC_OR: case FUNC_IMPLY_NATURAL: return sat ? 1.0 : -1.0;
-    case FUNC_EQUAL: return 1.0;
-    default: return sat ? 1.0 : 0.0;
-  }
-}
-double record_delta(const CompiledGraph &c, uint32_t e, bool owner_is_cat) {
-  const EdgeRec &r = c.edges[e];
-  if (r.packed & EDGE_FIXED_FLAG) return 0.0;
-  if (r.packed & EDGE_PRESIGNED) {
-    float miss;
-    std::memcpy(&miss, &r.aux, 4);
-    return std::fabs((double)r.fval - (double)miss);
-  }
-  const double f = (r.packed & EDGE_F64_FLAG) ? c.edge_fval64[e] : (double)r.fval;
-  const uint32_t ar = (r.packed & EDGE_INLINE2) ? 2u : ((r.packed >> EDGE_ARITY_SHIFT) & EDGE_ARITY_MASK);
-  if (ar <= 1u) {
-    const uint32_t fn = r.packed & EDGE_FUNC_MASK;
-    const double hit = host_unary_sign(fn, owner_is_cat || r.aux == 1u);
-    const double miss = host_unary_sign(fn, !owner_is_cat && r.aux == 0u);
-    return std::fabs(hit - miss) * std::fabs(f);
-  }
-  return 2.0 * std::fabs(f) * (double)(ar - 1u);
-}
-
-// Gershgorin bound of one variable's share of the batch curvature, per record: the variable's
-// SGD gradient over the weights has Jacobian kappa * d d^T for a boolean variable (logistic:
-// kappa = p (1 - p) <= 1/4, d = the records' deltas) and J^T (diag(p) - p p^T) J for a
-// categorical one (softmax over its value rows; absolute row sums of diag(p) - p p^T are
-// 2 p (1 - p) <= 1/2).  Row sum of |H| for weight w: sum over w's records r of
-//   1/4 * d_r * (sum of the row's deltas)              boolean
-//   1/2 * d_r * (largest sum of deltas of a value row) categorical.
-// fn(e, bound) is called for every record with a non-zero bound.
-template <class Fn>
-void for_each_record_bound(const CompiledGraph &c, uint32_t p, Fn &&fn) {
-  const uint32_t m = c.v_meta[p];
-  const bool cat = m & VM_CATEGORICAL;
-  double S = 0.0;
-  for (uint32_t r = c.v_row[p]; r < c.v_row[p + 1]; ++r) {
-    double sr = 0.0;
-    for (uint32_t e = c.row_ptr[r]; e < c.row_ptr[r + 1]; ++e) sr += record_delta(c, e, cat);
-    S = cat ? std::max(S, sr) : S + sr;
-  }
-  if (S == 0.0) return;
-  const double kappa = cat ? 0.5 : 0.25;
-  for (uint32_t e = c.row_ptr[c.v_row[p]]; e < c.row_ptr[c.v_row[p + 1]]; ++e) {
-    const double d = record_delta(c, e, cat);
-    if (d != 0.0) fn(e, kappa * d * S);
-  }
-}
-
 // A plan level's own weight-sorted layout (Level::sorted_supers): for a split plan cut ALONG its
 // chunks, as many super-tiles per chunk as workgroups are resident; for an un-split sweep, where a
 // launch holds query AND evidence tiles, one run per launch -- the default layout cuts those apart
@@ -839,7 +751,7 @@ void ensure_level_layout(dwx_sampler *s, dwx_sampler::Level *L, uint32_t batches
   if (tiles_in_chunks / L->chunks.size() < 8ull * c.sorted_slots) return;
   rt::set_device(s->device);
   SortedLayout lay;
-  const bool on_device = devb::available() && !getenv("DWX_HOST_BUILD");
+  const bool on_device = build_on_device();
   build_sorted_layout(c, ranges, c.sorted_per_super, c.sorted_slots, batches == 1, host_threads(), lay, on_device);
   if (lay.supers.empty()) return;
   SortRec8 *d_sorted = nullptr;
@@ -863,114 +775,6 @@ void ensure_level_layout(dwx_sampler *s, dwx_sampler::Level *L, uint32_t batches
   L->d_supers = d_supers;
 }
 
-// The domain of the learning sums.  A mini-batch adds, per weight, int64 sums in
-// fixed point: G += llrint(2^30 t g) and T += llrint(2^30 t) per visited record (DWX_BUF_GRAD), and the
-// static h = sum llrint(2^10 kappa d S) (for_each_record_bound).  Nothing on the sweep path saturates or
-// checks them -- a wrapped sum is a gradient of the wrong sign, and the oracle's schedule mode, which
-// restates the same containers, used to agree with it bit for bit -- so the domain is enforced here,
-// where a plan's mini-batches are made.  Per group of variables that share an update (`groups`:
-// device-order position ranges) and per weight, the WORST case of each sum over any assignment:
-//   G: a record's |g| = |pot_free - pot_evid| is at most its delta (record_delta: the two signs of a
-//      unary factor, 2 |f| (arity - 1) beyond); its visits carry a truthiness of 1 in all, or -- a
-//      categorical variable under noise_aware -- of at most the variable's total truthiness (row d is
-//      visited with t_d as the evidence row and with every other value's t as the proposal's row: up to one
-//      visit per value row, each rounding its own term, so one unit per value row is added on top);
-//   T: the same visits, 2^30 t each;   h: exactly the table's value.
-// Every term is rounded UP to an integer, so the true sum of every prefix, in any order, stays inside
-// the bound: the kernels' partial sums (LDS accumulators, block rows, per-record atomics) cannot wrap
-// either.  Sums in uint64, saturating: a bound of exactly 2^63 - 1 passes, 2^63 does not.
-// -> empty, or the text of the DWX_E_LIMIT error, naming the weight.
-std::string learning_range_error(dwx_sampler *s, const std::vector<std::pair<uint32_t, uint32_t>> &groups) {
-  const CompiledGraph &c = *s->cg;
-  const dwx_options &o = s->opts;
-  if (!c.W || groups.empty()) return std::string();
-  constexpr uint64_t kLimit = (uint64_t)INT64_MAX, kSat = UINT64_MAX;
-  const uint32_t nth = host_threads();
-  std::vector<uint64_t> acc(3 * c.W, 0);   // [G | T | h] bounds of the current group
-  auto sat_add = [](uint64_t *a, uint64_t v) -> uint64_t {   // -> the value before
-    uint64_t old = __atomic_load_n(a, __ATOMIC_RELAXED);
-    for (;;) {
-      const uint64_t next = old > kSat - v ? kSat : old + v;
-      if (__atomic_compare_exchange_n(a, &old, next, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) return old;
-    }
-  };
-  auto up = [](double x) -> uint64_t {   // ceil, saturating
-    return x >= 18446744073709549568.0 ? kSat : (uint64_t)std::ceil(x);
-  };
-  for (size_t k = 0; k < groups.size(); ++k) {
-    const uint32_t p0 = groups[k].first, p1 = groups[k].second;
-    const uint32_t T = std::max(1u, std::min<uint32_t>(nth, (p1 - p0) / 4096u + 1u));
-    std::vector<std::vector<uint32_t>> touched(T);
-    parallel_parts(p1 - p0, T, [&](uint32_t t, uint64_t b, uint64_t e) {
-      // a thread's adds go through a small direct-mapped cache: heavily tied weights (eight weights
-      // on 10^7 records) would otherwise be one contended cache line
-      struct Slot { uint32_t wid; uint64_t g, t, h; };
-      constexpr uint32_t kSlots = 64;
-      Slot cache[kSlots];
-      for (auto &sl : cache) sl = Slot{0xFFFFFFFFu, 0, 0, 0};
-      auto flush = [&](Slot &sl) {
-        if (sl.wid == 0xFFFFFFFFu) return;
-        const uint64_t before = sat_add(&acc[c.W + sl.wid], sl.t);
-        sat_add(&acc[sl.wid], sl.g);
-        sat_add(&acc[2 * c.W + sl.wid], sl.h);
-        if (before == 0) touched[t].push_back(sl.wid);
-        sl = Slot{0xFFFFFFFFu, 0, 0, 0};
-      };
-      auto slot_of = [&](uint32_t wid) -> Slot & {
-        Slot &sl = cache[wid % kSlots];
-        if (sl.wid != wid) { flush(sl); sl.wid = wid; }
-        return sl;
-      };
-      auto add = [](uint64_t &a, uint64_t v) { a = a > kSat - v ? kSat : a + v; };
-      for (uint32_t p = p0 + (uint32_t)b; p < p0 + (uint32_t)e; ++p) {
-        const uint32_t m = c.v_meta[p];
-        if (!triggers_sgd(o, m)) continue;
-        const bool cat = m & VM_CATEGORICAL;
-        double tt = 1.0;
-        if (cat && o.noise_aware) {
-          tt = 0.0;
-          if (!c.row_truth.empty())
-            for (uint32_t r = c.v_row[p]; r < c.v_row[p + 1]; ++r) tt += c.row_truth[r];
-        }
-        if (!(tt > 0.0)) continue;
-        // (such a record is visited up to once per value row, each visit rounding its own term: half a unit each)
-        const uint64_t visits_slack = cat && o.noise_aware ? c.v_row[p + 1] - c.v_row[p] : 0u;
-        const uint64_t t_up = up(FIX_SCALE * tt) + visits_slack;
-        for (uint32_t e2 = c.row_ptr[c.v_row[p]]; e2 < c.row_ptr[c.v_row[p + 1]]; ++e2) {
-          if (c.edges[e2].packed & EDGE_FIXED_FLAG) continue;
-          Slot &sl = slot_of(c.edges[e2].wid);
-          add(sl.t, t_up);
-          add(sl.g, up(FIX_SCALE * (tt * record_delta(c, e2, cat))));
-          add(sl.g, visits_slack);
-        }
-        for_each_record_bound(c, p, [&](uint32_t e2, double bound) {
-          add(slot_of(c.edges[e2].wid).h, up(H_SCALE * bound));
-        });
-      }
-      for (auto &sl : cache) flush(sl);
-    }, 4096);
-    uint32_t bad = 0xFFFFFFFFu;
-    for (const auto &list : touched)
-      for (uint32_t w : list)
-        if (acc[w] > kLimit || acc[c.W + w] > kLimit || acc[2 * c.W + w] > kLimit) bad = std::min(bad, w);
-    if (bad != 0xFFFFFFFFu) {
-      const uint64_t w = bad;
-      char buf[512];
-      const char *which = acc[bad] > kLimit ? "gradient sum (2^30 x sum of t |g|)"
-                          : (acc[2 * c.W + bad] > kLimit ? "curvature bound (2^10 x sum of kappa d S)" : "update count (2^30 x sum of t)");
-      const uint64_t v = acc[bad] > kLimit ? acc[bad] : (acc[2 * c.W + bad] > kLimit ? acc[2 * c.W + bad] : acc[c.W + bad]);
-      snprintf(buf, sizeof buf,
-               "the learning sums of weight %llu can leave int64 in mini-batch %zu of %zu: worst-case %s = %.17g%s, "
-               "the limit is 2^63 - 1 (fewer or smaller feature values on this weight, or a finer plan: dwx_sgd_plan's force_batches)",
-               (unsigned long long)w, k + 1, groups.size(), which, (double)v, v == kSat ? " or more" : "");
-      return buf;
-    }
-    for (const auto &list : touched)
-      for (uint32_t w : list) acc[w] = acc[c.W + w] = acc[2 * c.W + w] = 0;
-  }
-  return std::string();
-}
-
 // Everything a plan level needs to run its chunks without per-record atomics: per chunk,
 // (a) the static update counts of its boolean variables -- a boolean variable that triggers
 // SGD visits every factor of its row once with t = 1 (src/factor_graph.cc:265-273),
@@ -983,7 +787,6 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
   rt::set_device(s->device);
   const CompiledGraph &c = *s->cg;
   const dwx_options &o = s->opts;
-  const uint32_t nth = host_threads();
   std::unique_ptr<dwx_sampler::Level> L(new dwx_sampler::Level());
   // The pieces of a split sweep are visited ROUND-ROBIN over the colour launches, piece b of n
   // at position (b + 1/2) / n of the sweep: any order of independent sets is a Gibbs scan, and
@@ -996,7 +799,7 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
     struct Piece { double at; dwx_sampler::Chunk ch; };
     std::vector<Piece> pieces;
     for (size_t l = 0; l + 1 < c.launch_off.size(); ++l) {
-      const std::vector<uint32_t> cut = cut_launch(s, l, batches);
+      const std::vector<uint32_t> cut = cut_launch(c, s->sgd_work, s->sgd_work_max_launch, l, batches);
       const size_t n = cut.size() - 1;
       for (size_t b = 0; b < n; ++b)
         pieces.push_back({((double)b + 0.5) / (double)n, {(uint32_t)l, cut[b], cut[b + 1]}});
@@ -1004,8 +807,6 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
     std::stable_sort(pieces.begin(), pieces.end(), [](const Piece &a, const Piece &b) { return a.at < b.at; });
     for (const Piece &pc : pieces) L->chunks.push_back(pc.ch);
   }
-  // (plan_layouts 0, the default: with the level wherever the records are sorted on the device -- it
-  // costs milliseconds there; a host build pays 0.3 s per level and waits for 2048 sweeps)
   // DWX_TIMING=1: wall time of the level's build steps on stderr (each ends on a stream sync)
   const bool lv_timing = getenv("DWX_TIMING") != nullptr;
   auto lv_t0 = std::chrono::steady_clock::now();
@@ -1023,7 +824,7 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
     std::vector<std::pair<uint32_t, uint32_t>> groups;
     if (batches == 1) groups.push_back({c.tile_v.front(), c.tile_v.back()});
     else for (const auto &ch : L->chunks) groups.push_back({c.tile_v[ch.t0], c.tile_v[ch.t1]});
-    L->range_error = learning_range_error(s, groups);
+    L->range_error = learning_range_error(c, o, groups);
     lv_step("range of the learning sums");
     if (!L->range_error.empty()) {
       dwx_sampler::Level *ret = L.get();
@@ -1031,549 +832,156 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
       return ret;
     }
   }
-  if (s->opts.plan_layouts == 1 || (s->opts.plan_layouts == 0 && devb::available() && !getenv("DWX_HOST_BUILD")))
-    ensure_level_layout(s, L.get(), batches);
+  const bool on_device = build_on_device();
+  // (plan_layouts 0, the default: with the level wherever the records are sorted on the device -- it
+  // costs milliseconds there; a host build pays 0.3 s per level and waits for 2048 sweeps)
+  if (s->opts.plan_layouts == 1 || (s->opts.plan_layouts == 0 && on_device)) ensure_level_layout(s, L.get(), batches);
   lv_step("weight-sorted layout");
-  const uint32_t nc = (uint32_t)L->chunks.size();
   // beyond this the per-chunk tables cost more than they save: such plans keep the
   // per-record atomics and dynamic counts
   uint32_t table_chunks = 4 * MAX_PLAN_BATCHES;
-  if (const char *e = getenv("DWX_PLAN_TABLE_CHUNKS")) table_chunks = (uint32_t)std::max(1L, atol(e));   // test hook
-  L->fast = nc >= 1 && nc <= table_chunks && (uint64_t)nc * c.W * 16 <= ((uint64_t)2 << 30);
+  uint64_t min_w = 131072, bp_tiles = BP_TILES;   // (fewer weights: the list pull is as fast, tools/tied_sweep.py)
+  if (const char *e = getenv("DWX_PLAN_TABLE_CHUNKS")) table_chunks = (uint32_t)std::max(1L, atol(e));   // test hooks
+  if (const char *e = getenv("DWX_BLOCK_PULL_MIN_W")) min_w = (uint64_t)std::max(0L, atol(e));
+  if (const char *e = getenv("DWX_BLOCK_PULL_TILES")) bp_tiles = (uint64_t)std::min<long>(BP_TILES, std::max(1L, atol(e)));
+  const uint32_t n_chunks = (uint32_t)L->chunks.size();
+  L->fast = n_chunks >= 1 && n_chunks <= table_chunks && (uint64_t)n_chunks * c.W * 16 <= ((uint64_t)2 << 30);
   if (batches == 1) L->fast = true;
   if (L->fast && c.W) {
     // groups of the tables: the chunks of a split sweep (an update follows each of them); ONE
     // group for an un-split sweep, whatever its number of colour launches (one update at the end)
-    struct Group { uint32_t t0, t1; };
-    std::vector<Group> groups;
+    std::vector<hostb::TileGroup> groups;
     if (batches == 1) groups.push_back({0u, (uint32_t)c.tiles.size()});
     else for (const auto &ch : L->chunks) groups.push_back({ch.t0, ch.t1});
     const uint32_t nc = (uint32_t)groups.size();
-    std::vector<uint32_t> chunk_of(c.tiles.size(), 0);
-    for (uint32_t k = 0; k < nc; ++k)
-      for (uint32_t t = groups[k].t0; t < groups[k].t1; ++t) chunk_of[t] = k;
-    // (a) static tables, one row pair per group (rows are disjoint: groups in parallel): the
-    // update counts T of boolean variables and the curvature bounds h of all variables
-    // (apply_kernel's saturating step); row k = [T[W] | h[W]]
+    // (a) the static tables, one row pair [T[W] | h[W]] per group, and (b) the pull gradient's incidence list
+    // and block tables: built on the device (device_build.hip), or on the host (level_build.cc) and uploaded
+    // -- the same structures bit for bit
     L->rows = nc;
-    const bool tables_on_device = devb::available() && !getenv("DWX_HOST_BUILD");
-    if (tables_on_device) {
-      // (a) on the device: a lane per variable over the uploaded records, integer atomics (device_build.hip)
-      std::vector<uint32_t> group_of(c.tiles.size(), 0xFFFFFFFFu);
+    long long tm = 0, hm = 0;
+    devb::Incidence inc;
+    if (on_device) {
+      std::vector<uint32_t> group_of(c.tiles.size(), 0xFFFFFFFFu), tile_info(c.tiles.size(), 0xFFFFFFFFu);
       for (uint32_t k = 0; k < nc; ++k)
         for (uint32_t t = groups[k].t0; t < groups[k].t1; ++t) group_of[t] = k;
       L->d_t_static = (long long *)rt::dmalloc((size_t)nc * 2 * c.W * 8);
-      long long tm = 0, hm = 0;
       devb::build_static_tables(s->d_tiles, (uint32_t)c.tiles.size(), group_of.data(), s->d_v_meta, s->d_v_row, s->d_row_ptr,
                                 s->d_edges, s->d_edge_fval64, (const uint8_t *)s->d_w_fixed, (uint32_t)c.W, nc,
                                 o.learn_non_evidence != 0, o.noise_aware != 0, L->d_t_static, &tm, &hm, (void *)s->stream);
-      L->c_max = (double)hm / H_SCALE; L->t_max = (double)tm / FIX_SCALE;
       lv_step("static tables (device)");
-    } else {
-    RawArray<long long> ts((size_t)nc * 2 * c.W);
-    parallel_ranges((uint64_t)nc * 2 * c.W, nth, [&](uint64_t b, uint64_t e) { std::fill(ts.data() + b, ts.data() + e, 0LL); });
-    const long long one = (long long)FIX_SCALE;
-    // Few groups (the un-split level has ONE: a single thread used to walk all of config 5's 10^9
-    // records here): the variables of a group are shared out over the threads instead, which add
-    // into the group's rows atomically -- integer sums, the same tables in any order.
-    auto group_rows = [&](uint64_t k, uint32_t pb, uint32_t pe, auto &&add) {
-      long long *row = ts.data() + k * 2 * c.W, *hrow = row + c.W;
-      for (uint32_t p = pb; p < pe; ++p) {
-        const uint32_t m = c.v_meta[p];
-        if (!triggers_sgd(o, m)) continue;
-        for_each_record_bound(c, p, [&](uint32_t e, double bound) {
-          add(&hrow[c.edges[e].wid], (long long)std::llrint(H_SCALE * bound));
-        });
-        if (m & VM_CATEGORICAL) continue;   // (their counts depend on the samples: dynamic)
-        for (uint32_t e = c.row_ptr[c.v_row[p]]; e < c.row_ptr[c.v_row[p] + 1]; ++e)
-          if (!c.w_fixed[c.edges[e].wid]) add(&row[c.edges[e].wid], one);
-      }
-    };
-    if (nc >= nth || nth <= 1) {
-      parallel_ranges(nc, std::min(nth, nc), [&](uint64_t kb, uint64_t ke) {
-        for (uint64_t k = kb; k < ke; ++k)
-          group_rows(k, c.tile_v[groups[k].t0], c.tile_v[groups[k].t1], [](long long *a, long long v) { *a += v; });
-      }, 2);
-    } else {
-      for (uint64_t k = 0; k < nc; ++k) {
-        const uint32_t p0 = c.tile_v[groups[k].t0], p1 = c.tile_v[groups[k].t1];
-        parallel_ranges(p1 - p0, nth, [&](uint64_t b, uint64_t e) {
-          group_rows(k, p0 + (uint32_t)b, p0 + (uint32_t)e,
-                     [](long long *a, long long v) { __atomic_fetch_add(a, v, __ATOMIC_RELAXED); });
-        });
-      }
-    }
-    {
-      const uint32_t T = std::max(1u, std::min(nth, 16u));
-      std::vector<double> hm(T, 0.0), tm(T, 0.0);
-      parallel_parts((uint64_t)nc * c.W, T, [&](uint32_t t, uint64_t b, uint64_t e) {
-        long long h = 0, tt = 0;
-        for (uint64_t i = b; i < e; ++i) {
-          const uint64_t k = i / c.W, w = i % c.W;
-          tt = std::max(tt, ts[k * 2 * c.W + w]);
-          h = std::max(h, ts[(k * 2 + 1) * c.W + w]);
-        }
-        hm[t] = (double)h / H_SCALE; tm[t] = (double)tt / FIX_SCALE;
-      }, 0);
-      for (uint32_t t = 0; t < T; ++t) { L->c_max = std::max(L->c_max, hm[t]); L->t_max = std::max(L->t_max, tm[t]); }
-    }
-    L->d_t_static = upload_raw(ts.data(), (size_t)nc * 2 * c.W, s->stream);
-    rt::stream_sync(s->stream);      // (ts dies with this scope)
-    }
-    // (b) incidence list
-    if (tables_on_device) {
-      // on the device (device_build.hip): ordered emit per tile, one stable radix sort by (chunk, weight),
-      // the block tables filled by a lane per weight -- the structures below, bit for bit
-      uint64_t min_w = 131072, bp_tiles = BP_TILES;
-      if (const char *e = getenv("DWX_BLOCK_PULL_MIN_W")) min_w = (uint64_t)std::max(0L, atol(e));          // test hooks
-      if (const char *e = getenv("DWX_BLOCK_PULL_TILES")) bp_tiles = (uint64_t)std::min<long>(BP_TILES, std::max(1L, atol(e)));
-      std::vector<uint32_t> tile_info(c.tiles.size(), 0xFFFFFFFFu);
       for (size_t ti = 0; ti < c.tiles.size(); ++ti) {
         const TileDesc &td = c.tiles[ti];
         const bool unary_only = !(td.flags & TILE_PULL) && (td.flags & TILE_PULL_UNARY) && c.ecap <= 6 * BLOCK_THREADS;
         if ((!(td.flags & TILE_PULL) && !unary_only) || (td.flags & TILE_OUTSIDE)) continue;
-        tile_info[ti] = chunk_of[ti] | ((unary_only ? 2u : 1u) << 30);
+        tile_info[ti] = group_of[ti] | ((unary_only ? 2u : 1u) << 30);   // (the groups cover every tile: the launches do)
       }
-      devb::Incidence inc;
       devb::build_incidence(s->d_tiles, c.tiles.data(), (uint32_t)c.tiles.size(), tile_info.data(), s->d_v_meta, s->d_v_row,
                             s->d_row_ptr, s->d_edges, o.learn_non_evidence != 0, o.noise_aware != 0, (uint32_t)c.W, nc, min_w,
                             (uint32_t)bp_tiles, inc, (void *)s->stream);
-      L->d_inc_wid = inc.d_inc_wid; L->d_inc_slot = inc.d_inc_slot; L->d_inc_d = inc.d_inc_d;
-      L->inc_begin = inc.inc_begin; L->inc_end = inc.inc_end;
-      lv_step("incidence list (device)");
-      if (!inc.bp.empty()) {
-        const bool bp_timing = getenv("DWX_TIMING") != nullptr;
-        L->bp.resize(nc);
-        for (uint32_t k = 0; k < nc; ++k) {
-          if (!inc.bp[k].blocks) continue;
-          dwx_sampler::Level::BlockTable &bt = L->bp[k];
-          bt.d_ell = inc.bp[k].d_ell;
-          bt.d_ov_start = inc.bp[k].d_ov_start;
-          bt.d_tile0 = upload(inc.bp[k].tile0, s->stream);
-          bt.blocks = inc.bp[k].blocks; bt.depth = inc.bp[k].depth;
-          bt.parts = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rt::cu_count() / bt.blocks, inc.wp / BP_THREADS));
-          if (bp_timing)
-            fprintf(stderr, "[dwx block pull] group %u: %u blocks x depth %u (%u entries, %llu bytes of rows), %zu deltas, %llu of %llu entries on the list (device build)\n",
-                    k, bt.blocks, bt.depth, bt.depth * (inc.dvals.size() == 1 ? BP_PK_ROW : BP_ROW),
-                    (unsigned long long)((uint64_t)bt.blocks * bt.depth * inc.wp * (inc.dvals.size() == 1 ? 8 : 16)), inc.dvals.size(),
-                    (unsigned long long)inc.bp[k].on_list, (unsigned long long)inc.bp[k].total);
-        }
-        std::vector<long long> qtab(inc.dvals.size());
-        for (size_t i = 0; i < inc.dvals.size(); ++i) {
-          float d; std::memcpy(&d, &inc.dvals[i], 4);
-          qtab[i] = std::llrint(FIX_SCALE * (double)d);
-        }
-        L->d_bp_qtab = upload(qtab, s->stream);
-        L->d_bp_partial = (long long *)rt::dmalloc(inc.max_blocks * inc.wp * 8);
-        L->bp_deltas = (uint32_t)inc.dvals.size(); L->bp_wp = (uint32_t)inc.wp;
-        rt::allow_dynamic_lds(pull_ell_kernel<1, false>, BP_LDS_BYTES);
-        rt::allow_dynamic_lds(pull_ell_kernel<2, false>, BP_LDS_BYTES);
-        rt::allow_dynamic_lds(pull_ell_kernel<1, true, true>, BP_LDS_BYTES);
-        rt::allow_dynamic_lds(pull_ell_kernel<2, true, true>, BP_LDS_BYTES);
-        rt::allow_dynamic_lds(pull_ell_kernel<3, true, true>, BP_LDS_BYTES);
-        rt::allow_dynamic_lds(pull_ell_kernel<4, true, true>, BP_LDS_BYTES);
-      }
+    } else {
+      RawArray<long long> ts;
+      hostb::build_static_tables(c, o, groups, ts, &tm, &hm);
+      L->d_t_static = upload(ts, s->stream);
       rt::stream_sync(s->stream);
-    } else {
-    struct Inc { uint32_t wid, slot; float d; uint32_t chunk; };
-    RawArray<Inc> by_w, by_c;
-    std::vector<uint64_t> w_start, c_start;
-    parallel_group_by_key<Inc>(
-        c.tiles.size(), nth, c.W, [](const Inc &r) { return (uint64_t)r.wid; },
-        [&](uint64_t tb, uint64_t te, auto &&emit) {
-          for (uint64_t ti = tb; ti < te; ++ti) {
-            const TileDesc &td = c.tiles[ti];
-            // (TILE_PULL_UNARY: only the tile's pre-signed records; not in a K = 12 build, whose
-            // kernels walk such tiles generically)
-            const bool unary_only = !(td.flags & TILE_PULL) && (td.flags & TILE_PULL_UNARY) && c.ecap <= 6 * BLOCK_THREADS;
-            if (!(td.flags & TILE_PULL) && !unary_only) continue;
-            if (td.flags & TILE_OUTSIDE) continue;   // giant_kernel / wide_kernel: atomics
-            for (uint32_t l = 0; l < td.nv; ++l) {
-              const uint32_t p = td.v0 + l, m = c.v_meta[p];
-              if (!(o.learn_non_evidence || (!o.noise_aware && (m & VM_EVIDENCE)))) continue;
-              for (uint32_t e = c.row_ptr[c.v_row[p]]; e < c.row_ptr[c.v_row[p] + 1]; ++e) {
-                const EdgeRec &r = c.edges[e];
-                if (r.packed & EDGE_FIXED_FLAG) continue;
-                if (unary_only && !(r.packed & EDGE_PRESIGNED)) continue;
-                float miss;
-                std::memcpy(&miss, &r.aux, 4);
-                const float dd = r.fval - miss;    // exact: |hit| == |miss| or one of them is 0
-                if (dd == 0.0f) continue;
-                emit(Inc{r.wid, (uint32_t)(ti * BLOCK_THREADS + l), dd, chunk_of[ti]});
-              }
-            }
-          }
-        },
-        by_w, w_start, 64);
-    const uint64_t n_inc = by_w.size();
-    if (n_inc + (uint64_t)nc * PULL_RUN >= 0xFFFFFFFFull)
-      throw std::invalid_argument("incidence list exceeds 2^32-1 entries");
-    // the groups' lists: by weight inside a group
-    const RawArray<Inc> *src = &by_w;
-    if (nc > 1) {
-      parallel_group_by_key<Inc>(
-          n_inc, nth, nc, [](const Inc &r) { return (uint64_t)r.chunk; },
-          [&](uint64_t b, uint64_t e, auto &&emit) { for (uint64_t i = b; i < e; ++i) emit(by_w[i]); },
-          by_c, c_start);
-      by_w.clear();
-      src = &by_c;
-    } else {
-      c_start = {0, n_inc};
-    }
-    // Block pull (graphs with many weights): per group, rows of BP_ROW * depth entries per
-    // (variable block, weight) for pull_ell_kernel; an entry beyond its row stays on the list.
-    RawArray<Inc> kept;                    // the lists of all groups after the tables took their entries
-    std::vector<uint64_t> kept_start;
-    {
-      uint64_t min_w = 131072, bp_tiles = BP_TILES;   // (below: the list pull is as fast, tools/tied_sweep.py)
-      if (const char *e = getenv("DWX_BLOCK_PULL_MIN_W")) min_w = (uint64_t)std::max(0L, atol(e));          // test hooks
-      if (const char *e = getenv("DWX_BLOCK_PULL_TILES")) bp_tiles = (uint64_t)std::min<long>(BP_TILES, std::max(1L, atol(e)));
-      const bool bp_timing = getenv("DWX_TIMING") != nullptr;
-      // the distinct record deltas (few: feature values repeat), as fixed-point steps
-      std::vector<uint32_t> dvals;
-      bool enabled = n_inc && c.W >= min_w;
-      if (enabled) {
-        const uint32_t T = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nth, n_inc / 65536));
-        std::vector<std::vector<uint32_t>> local(T);
-        parallel_parts(n_inc, T, [&](uint32_t t, uint64_t b, uint64_t e) {
-          std::vector<uint32_t> &v = local[t];
-          uint32_t last = 0; bool have = false;
-          for (uint64_t i = b; i < e && v.size() <= 4 * BP_MAX_DELTAS; ++i) {
-            uint32_t bits; std::memcpy(&bits, &(*src)[i].d, 4);
-            if (have && bits == last) continue;
-            last = bits; have = true;
-            v.push_back(bits);
-            if (v.size() % 4096 == 0) { std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); }
-          }
-          std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end());
-        }, 0);
-        for (auto &v : local) dvals.insert(dvals.end(), v.begin(), v.end());
-        std::sort(dvals.begin(), dvals.end()); dvals.erase(std::unique(dvals.begin(), dvals.end()), dvals.end());
-        enabled = dvals.size() <= BP_MAX_DELTAS;
-      }
-      if (enabled) {
-        const uint64_t Wp = (c.W + BP_THREADS - 1) / BP_THREADS * BP_THREADS;
-        L->bp.resize(nc);
-        uint64_t max_blocks = 0;
-        std::vector<uint64_t> ov_count(nc, 0);
-        std::vector<std::vector<uint64_t>> ov_start(nc);   // per group, per weight: entries left on the list
-        std::vector<RawArray<Inc>> ov(nc);
-        std::vector<uint8_t> has(c.tiles.size(), 0);
-        std::vector<uint32_t> block_of(c.tiles.size(), 0);
-        for (uint32_t k = 0; k < nc; ++k) {
-          const Inc *ent = src->data() + c_start[k];
-          const uint64_t n = c_start[k + 1] - c_start[k];
-          if (!n) continue;
-          // (1) blocks: runs of <= bp_tiles consecutive tiles, started at tiles that own entries
-          std::fill(has.begin(), has.end(), 0);
-          parallel_ranges(n, nth, [&](uint64_t b, uint64_t e) {
-            for (uint64_t i = b; i < e; ++i) {   // (test first: the flags are shared by all threads)
-              uint8_t &h = has[ent[i].slot / BLOCK_THREADS];
-              if (!h) h = 1;
-            }
-          });
-          std::vector<uint32_t> tile0;
-          for (uint32_t ti = 0; ti < c.tiles.size(); ++ti) {
-            if (!has[ti]) continue;
-            if (tile0.empty() || ti >= tile0.back() + bp_tiles) tile0.push_back(ti);
-            block_of[ti] = (uint32_t)tile0.size() - 1;
-          }
-          const uint64_t nvb = tile0.size();
-          const double lambda = (double)n / ((double)c.W * (double)nvb);
-          if (lambda < 0.5) continue;   // nearly empty rows: this group keeps its list
-          const bool packed = dvals.size() == 1;       // one delta: three 19-bit slots per 8-byte word
-          const uint32_t depth = bp_row_depth(lambda, packed), cap = (packed ? BP_PK_ROW : BP_ROW) * depth;
-          // (2) where each weight's entries start inside the group (they are sorted by weight)
-          std::vector<uint64_t> w_at(c.W + 1, n);
-          parallel_ranges(n, nth, [&](uint64_t b, uint64_t e) {
-            for (uint64_t i = b; i < e; ++i) {
-              const uint32_t w = ent[i].wid, prev = i ? ent[i - 1].wid + 1 : 0;
-              if (!i || ent[i - 1].wid != w) for (uint32_t x = prev; x <= w; ++x) w_at[x] = i;
-            }
-          });
-          // (3) the table; entries of one weight come in tile order: blocks ascending
-          RawArray<unsigned long long> ell8(nvb * depth * Wp * (packed ? 1 : 2));   // (8-byte words: U32x4 rows are two)
-          U32x4 *ell = (U32x4 *)ell8.data();
-          parallel_ranges(ell8.size(), nth, [&](uint64_t b, uint64_t e) { std::memset((void *)(ell8.data() + b), packed ? 0 : 0xFF, (e - b) * 8); });
-          std::vector<uint64_t> &ovs = ov_start[k];
-          ovs.assign(c.W + 1, 0);
-          parallel_ranges(c.W, nth, [&](uint64_t wb, uint64_t we) {
-            for (uint64_t w = wb; w < we; ++w) {
-              uint32_t cur = ~0u, kk = 0;
-              uint64_t o = 0;
-              for (uint64_t i = w_at[w]; i < w_at[w + 1]; ++i) {
-                const Inc &r = ent[i];
-                const uint32_t ti = r.slot / BLOCK_THREADS, vb = block_of[ti];
-                if (vb != cur) { cur = vb; kk = 0; }
-                if (kk < cap && packed) {
-                  unsigned long long &word = ell8[((uint64_t)vb * depth + kk / BP_PK_ROW) * Wp + w];
-                  word = bp_pack_entry(word, kk % BP_PK_ROW, (ti - tile0[vb]) * BLOCK_THREADS + r.slot % BLOCK_THREADS);
-                } else if (kk < cap) {
-                  uint32_t bits; std::memcpy(&bits, &r.d, 4);
-                  const uint32_t di = (uint32_t)(std::lower_bound(dvals.begin(), dvals.end(), bits) - dvals.begin());
-                  ell[((uint64_t)vb * depth + kk / BP_ROW) * Wp + w].v[kk % BP_ROW] =
-                      ((ti - tile0[vb]) * BLOCK_THREADS + r.slot % BLOCK_THREADS) | (di << BP_SLOT_BITS);
-                } else {
-                  ++o;
-                }
-                ++kk;
-              }
-              ovs[w + 1] = o;
-            }
-          });
-          for (uint64_t w = 0; w < c.W; ++w) ovs[w + 1] += ovs[w];
-          ov_count[k] = ovs[c.W];
-          // the entries the rows could not take, in list order (same walk, now copying)
-          ov[k].reset(ov_count[k]);
-          if (ov_count[k]) {
-            Inc *dst = ov[k].data();
-            parallel_ranges(c.W, nth, [&](uint64_t wb, uint64_t we) {
-              for (uint64_t w = wb; w < we; ++w) {
-                uint32_t cur = ~0u, kk = 0;
-                uint64_t o = ovs[w];
-                for (uint64_t i = w_at[w]; i < w_at[w + 1]; ++i) {
-                  const uint32_t vb = block_of[ent[i].slot / BLOCK_THREADS];
-                  if (vb != cur) { cur = vb; kk = 0; }
-                  if (kk >= cap) dst[o++] = ent[i];
-                  ++kk;
-                }
-              }
-            });
-          }
-          dwx_sampler::Level::BlockTable &bt = L->bp[k];
-          bt.d_ell = (U32x4 *)upload_raw(ell8.data(), ell8.size(), s->stream);
-          bt.d_tile0 = upload(tile0, s->stream);
-          std::vector<uint32_t> ovs32(ovs.begin(), ovs.end());   // (< 2^32: the whole list is)
+      ts.clear();
+      lv_step("static tables (host)");
+      hostb::Incidence h;
+      hostb::build_incidence(c, o, groups, min_w, bp_tiles, h);
+      inc.inc_begin = h.inc_begin; inc.inc_end = h.inc_end;
+      inc.dvals = h.dvals; inc.max_blocks = h.max_blocks; inc.wp = h.wp;
+      try {
+        if (h.inc_wid.size()) {
+          inc.d_inc_wid = upload(h.inc_wid, s->stream);
+          inc.d_inc_slot = upload(h.inc_slot, s->stream);
+          inc.d_inc_d = upload(h.inc_d, s->stream);
+        }
+        inc.bp.resize(h.bp.size());
+        for (size_t k = 0; k < h.bp.size(); ++k) {
+          if (!h.bp[k].blocks) continue;
+          devb::Incidence::BlockTable &bt = inc.bp[k];
+          bt.d_ell = (U32x4 *)upload(h.bp[k].ell, s->stream);
+          const std::vector<uint32_t> ovs32(h.bp[k].ov_start.begin(), h.bp[k].ov_start.end());   // (< 2^32: the whole list is)
           bt.d_ov_start = upload(ovs32, s->stream);
-          bt.blocks = (uint32_t)nvb; bt.depth = depth;
-          // parts per block: one workgroup per CU over all blocks (it owns the CU's whole LDS)
-          bt.parts = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rt::cu_count() / nvb, Wp / BP_THREADS));
-          max_blocks = std::max(max_blocks, nvb);
-          rt::stream_sync(s->stream);   // ell dies with this scope
-          if (bp_timing)
-            fprintf(stderr, "[dwx block pull] group %u: %llu blocks x depth %u (%u entries, %llu bytes of rows), %zu deltas, %llu of %llu entries on the list\n",
-                    k, (unsigned long long)nvb, depth, cap, (unsigned long long)(ell8.size() * 8), dvals.size(), (unsigned long long)ov_count[k], (unsigned long long)n);
+          bt.tile0 = h.bp[k].tile0;
+          bt.blocks = h.bp[k].blocks; bt.depth = h.bp[k].depth; bt.total = h.bp[k].total; bt.on_list = h.bp[k].on_list;
+          rt::stream_sync(s->stream);   // (ovs32 dies with this scope, and the group's rows at once)
+          h.bp[k].ell.clear();
         }
-        if (max_blocks) {
-          // the lists shrink to what the tables left (same order: by weight inside a group)
-          kept_start.assign(nc + 1, 0);
-          for (uint32_t k = 0; k < nc; ++k)
-            kept_start[k + 1] = kept_start[k] + (L->bp[k].blocks ? ov_count[k] : c_start[k + 1] - c_start[k]);
-          kept.reset(kept_start[nc]);
-          for (uint32_t k = 0; k < nc; ++k) {
-            const Inc *ent = src->data() + c_start[k];
-            const uint64_t n = c_start[k + 1] - c_start[k];
-            Inc *dst = kept.data() + kept_start[k];
-            if (!L->bp[k].blocks) std::copy(ent, ent + n, dst);
-            else std::copy(ov[k].data(), ov[k].data() + ov[k].size(), dst);
-          }
-          std::vector<long long> qtab(dvals.size());
-          for (size_t i = 0; i < dvals.size(); ++i) {
-            float d; std::memcpy(&d, &dvals[i], 4);
-            qtab[i] = std::llrint(FIX_SCALE * (double)d);
-          }
-          L->d_bp_qtab = upload(qtab, s->stream);
-          L->d_bp_partial = (long long *)rt::dmalloc(max_blocks * Wp * 8);
-          L->bp_deltas = (uint32_t)dvals.size(); L->bp_wp = (uint32_t)Wp;
-          rt::allow_dynamic_lds(pull_ell_kernel<1, false>, BP_LDS_BYTES);
-          rt::allow_dynamic_lds(pull_ell_kernel<2, false>, BP_LDS_BYTES);
-          rt::allow_dynamic_lds(pull_ell_kernel<1, true, true>, BP_LDS_BYTES);
-          rt::allow_dynamic_lds(pull_ell_kernel<2, true, true>, BP_LDS_BYTES);
-          rt::allow_dynamic_lds(pull_ell_kernel<3, true, true>, BP_LDS_BYTES);
-          rt::allow_dynamic_lds(pull_ell_kernel<4, true, true>, BP_LDS_BYTES);
-          rt::stream_sync(s->stream);
-          by_w.clear(); by_c.clear();
-          src = &kept;
-          c_start = kept_start;
-        } else {
-          L->bp.clear();
-        }
+        rt::stream_sync(s->stream);     // (the host columns and rows die with this scope)
+      } catch (...) {
+        rt::dfree(inc.d_inc_wid); rt::dfree(inc.d_inc_slot); rt::dfree(inc.d_inc_d);
+        for (auto &t : inc.bp) { rt::dfree(t.d_ell); rt::dfree(t.d_ov_start); }
+        throw;
       }
     }
-    // columns; every chunk padded to whole runs with neutral entries (its last weight, zero
-    // contribution), so the kernel's 16-byte loads never leave the chunk
-    std::vector<uint64_t> off(nc + 1, 0);
-    for (uint32_t k = 0; k < nc; ++k)
-      off[k + 1] = off[k] + (c_start[k + 1] - c_start[k] + PULL_RUN - 1) / PULL_RUN * PULL_RUN;
-    const uint64_t padded = off[nc];
-    L->inc_begin.resize(nc); L->inc_end.resize(nc);
-    if (padded) {
-      RawArray<uint32_t> iw(padded), is(padded);
-      RawArray<float> id(padded);
+    // the level adopts the structures, whoever built them
+    L->c_max = (double)hm / H_SCALE; L->t_max = (double)tm / FIX_SCALE;
+    L->d_inc_wid = inc.d_inc_wid; L->d_inc_slot = inc.d_inc_slot; L->d_inc_d = inc.d_inc_d;
+    L->inc_begin = inc.inc_begin; L->inc_end = inc.inc_end;
+    L->bp.resize(inc.bp.size());
+    for (size_t k = 0; k < inc.bp.size(); ++k) { L->bp[k].d_ell = inc.bp[k].d_ell; L->bp[k].d_ov_start = inc.bp[k].d_ov_start; }
+    lv_step(on_device ? "incidence list (device)" : "incidence list (host)");
+    if (!inc.bp.empty()) {
+      const bool packed = inc.dvals.size() == 1;   // one delta: three 19-bit slots per 8-byte word
       for (uint32_t k = 0; k < nc; ++k) {
-        L->inc_begin[k] = (uint32_t)off[k]; L->inc_end[k] = (uint32_t)off[k + 1];
-        const uint64_t n = c_start[k + 1] - c_start[k], base = c_start[k];
-        parallel_ranges(off[k + 1] - off[k], nth, [&](uint64_t b, uint64_t e) {
-          for (uint64_t i = b; i < e; ++i) {
-            const Inc &r = (*src)[base + std::min(i, n - 1)];
-            iw[off[k] + i] = r.wid; is[off[k] + i] = r.slot; id[off[k] + i] = i < n ? r.d : 0.0f;
-          }
-        });
+        if (!inc.bp[k].blocks) continue;
+        dwx_sampler::Level::BlockTable &bt = L->bp[k];
+        bt.d_tile0 = upload(inc.bp[k].tile0, s->stream);
+        bt.blocks = inc.bp[k].blocks; bt.depth = inc.bp[k].depth;
+        // parts per block: one workgroup per CU over all blocks (it owns the CU's whole LDS)
+        bt.parts = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rt::cu_count() / bt.blocks, inc.wp / BP_THREADS));
+        if (lv_timing)
+          fprintf(stderr, "[dwx block pull] group %u: %u blocks x depth %u (%u entries, %llu bytes of rows), %zu deltas, %llu of %llu entries on the list (%s build)\n",
+                  k, bt.blocks, bt.depth, bt.depth * (packed ? BP_PK_ROW : BP_ROW),
+                  (unsigned long long)((uint64_t)bt.blocks * bt.depth * inc.wp * (packed ? 8 : 16)), inc.dvals.size(),
+                  (unsigned long long)inc.bp[k].on_list, (unsigned long long)inc.bp[k].total, on_device ? "device" : "host");
       }
-      L->d_inc_wid = upload_raw(iw.data(), padded, s->stream);
-      L->d_inc_slot = upload_raw(is.data(), padded, s->stream);
-      L->d_inc_d = upload_raw(id.data(), padded, s->stream);
-      rt::stream_sync(s->stream);   // the columns die with this scope
+      std::vector<long long> qtab(inc.dvals.size());
+      for (size_t i = 0; i < inc.dvals.size(); ++i) {
+        float d; std::memcpy(&d, &inc.dvals[i], 4);
+        qtab[i] = std::llrint(FIX_SCALE * (double)d);
+      }
+      L->d_bp_qtab = upload(qtab, s->stream);
+      L->d_bp_partial = (long long *)rt::dmalloc(inc.max_blocks * inc.wp * 8);
+      L->bp_deltas = (uint32_t)inc.dvals.size(); L->bp_wp = (uint32_t)inc.wp;
+      rt::allow_dynamic_lds(pull_ell_kernel<1, false>, BP_LDS_BYTES);
+      rt::allow_dynamic_lds(pull_ell_kernel<2, false>, BP_LDS_BYTES);
+      rt::allow_dynamic_lds(pull_ell_kernel<1, true, true>, BP_LDS_BYTES);
+      rt::allow_dynamic_lds(pull_ell_kernel<2, true, true>, BP_LDS_BYTES);
+      rt::allow_dynamic_lds(pull_ell_kernel<3, true, true>, BP_LDS_BYTES);
+      rt::allow_dynamic_lds(pull_ell_kernel<4, true, true>, BP_LDS_BYTES);
     }
-    }
-    rt::stream_sync(s->stream);
+    rt::stream_sync(s->stream);   // (qtab and the tile0 lists die with this scope)
   }
   dwx_sampler::Level *out = L.get();
   s->levels[batches] = std::move(L);
   return out;
 }
 
-// Curvature of one SGD mini-batch in weight space, when every colour launch is cut into
-// `batches` runs of tiles.  A variable v that triggers SGD contributes kappa_v d_v d_v^T to
-// the batch Hessian bound, d_v[w] = sum of |d_r| over its non-fixed records with weight w,
-// d_r = the change of the record's potential between proposals (|sign(hit) f - sign(miss) f|
-// for pre-signed records, a 2|f|(arity-1) bound otherwise), kappa = 1/4 (logistic) for
-// boolean, 1/2 for categorical variables.  The largest eigenvalue lambda of that matrix
-// decides whether ONE batched step tracks the reference's sequential updates
-// (stepsize * lambda < 2).  Estimated per chunk by two power iterations from the all-ones
-// vector (the matrix is entrywise non-negative: the iteration converges from below to its
-// Perron value) combined with the largest diagonal entry (exact for a batch dominated by
-// one heavily tied weight), times a safety factor; the result is the max over chunks.
+// Curvature of one SGD mini-batch in weight space, when every colour launch is cut into `batches` runs
+// of tiles: the largest eigenvalue lambda of the batch Hessian bound (hostb::batch_curvature,
+// devb::batch_curvature) decides whether ONE batched step tracks the reference's sequential updates
+// (stepsize * lambda < 2).  Estimated per chunk, times a safety factor; the result is the max over chunks.
 double row_sum_bound(dwx_sampler *s, uint32_t batches) {
   auto it = s->row_sum_cache.find(batches);
   if (it != s->row_sum_cache.end()) return it->second;
   const CompiledGraph &c = *s->cg;
-  std::vector<double> x(c.W, 0.0), y(c.W, 0.0), diag(c.W, 0.0);
-  devb::CurvatureScratch dev_sc;      // (device vectors of the batches estimated on the device, kept over the chunks)
-  std::vector<uint8_t> seen(c.W, 0);
-  std::vector<uint32_t> touched;
+  const bool on_device = build_on_device();
+  if (on_device) rt::set_device(s->device);
+  devb::CurvatureScratch dev_sc;      // (the vectors of either estimate, kept over the chunks)
+  hostb::CurvatureScratch host_sc;
   double lam_max = 0.0;
-  auto rec_d = [&](uint32_t e, bool cat) -> double { return record_delta(c, e, cat); };
-  auto triggers = [&](uint32_t m) {
-    return s->opts.learn_non_evidence || (!s->opts.noise_aware && (m & VM_EVIDENCE)) ||
-           (s->opts.noise_aware && (m & VM_TRUTHINESS));
-  };
   for (size_t l = 0; l + 1 < c.launch_off.size(); ++l) {
-    const std::vector<uint32_t> cut = cut_launch(s, l, batches);
+    const std::vector<uint32_t> cut = cut_launch(c, s->sgd_work, s->sgd_work_max_launch, l, batches);
     for (size_t b = 0; b + 1 < cut.size(); ++b) {
       const uint32_t ta = cut[b], tb = cut[b + 1];
       if (s->sgd_work[tb] == s->sgd_work[ta]) continue;   // nothing learns in this run
       const uint32_t p0 = c.tile_v[ta], p1 = c.tile_v[tb];
-      // y = H x, three times: x0 = 1 (y = row sums), then two normalised power steps
-      double lam = 0.0, dmax = 0.0;
-      if ((uint64_t)(p1 - p0) * 8 >= c.W && p1 - p0 >= 65536 && devb::available() && !getenv("DWX_HOST_BUILD")) {
-        // ... on the device: the arithmetic of the branch below, term for term (device_build.hip)
-        rt::set_device(s->device);
-        const double v = devb::batch_curvature(p0, p1, s->d_v_meta, s->d_v_row, s->d_row_ptr, s->d_edges, s->d_edge_fval64,
-                                               s->opts.learn_non_evidence != 0, s->opts.noise_aware != 0, (uint32_t)c.W, dev_sc,
-                                               (void *)s->stream);
-        lam = v; dmax = 0.0;
-      } else if ((uint64_t)(p1 - p0) * 8 >= c.W && p1 - p0 >= 65536) {
-        // a batch that touches a good part of the weight table: variable ranges in parallel on ALL host
-        // threads, ONE shared y (and diagonal) in 64-bit FIXED POINT -- integer atomic adds: the sums
-        // do not depend on the order, lambda is reproducible -- and dense passes over the table.
-        // (Round 4: this was one private f64 vector per thread, hence 16 threads at most and a merge
-        // pass over 16 W doubles per iteration: 6 s of config 5's sampler create at W = 10 M.)
-        const uint32_t T = host_threads();
-        // bound of one term kappa d dot (x <= 1 entrywise: dot <= the variable's sum of deltas) and of
-        // a weight's number of terms, for the scale
-        std::vector<double> umax(T, 0.0), dmx(T, 0.0);
-        std::vector<uint64_t> nrec(T, 0);
-        parallel_parts(p1 - p0, T, [&](uint32_t t, uint64_t b, uint64_t e) {
-          double u = 0.0, dm = 0.0;
-          uint64_t n = 0;
-          for (uint32_t p = p0 + (uint32_t)b; p < p0 + (uint32_t)e; ++p) {
-            const uint32_t m = c.v_meta[p];
-            if (!triggers(m)) continue;
-            const bool cat = (m & VM_CATEGORICAL) != 0;
-            const uint32_t e0 = c.row_ptr[c.v_row[p]], e1 = c.row_ptr[c.v_row[p + 1]];
-            double S = 0.0, dv = 0.0;
-            for (uint32_t k = e0; k < e1; ++k) { const double d = rec_d(k, cat); S += d; dv = std::max(dv, d); }
-            u = std::max(u, (cat ? 0.5 : 0.25) * dv * S);
-            dm = std::max(dm, (cat ? 0.5 : 0.25) * dv * dv);
-            n += e1 - e0;
-          }
-          umax[t] = u; dmx[t] = dm; nrec[t] = n;
-        }, 0);
-        double U = 0.0, D2 = 0.0;
-        uint64_t R = 0;
-        for (uint32_t t = 0; t < T; ++t) { U = std::max(U, umax[t]); D2 = std::max(D2, dmx[t]); R += nrec[t]; }
-        if (U > 0.0 && R > 0) {
-        const double scale = std::ldexp(1.0, 62) / ((double)R * U), dscale = std::ldexp(1.0, 62) / ((double)R * D2);
-        RawArray<long long> yfix(c.W), dfix(c.W);
-        parallel_ranges(c.W, T, [&](uint64_t b, uint64_t e) { for (uint64_t w = b; w < e; ++w) { yfix[w] = 0; dfix[w] = 0; } });
-        std::fill(x.begin(), x.end(), 1.0);
-        for (int iter = 0; iter < 3; ++iter) {
-          parallel_parts(p1 - p0, T, [&](uint32_t, uint64_t b, uint64_t e) {
-            for (uint32_t p = p0 + (uint32_t)b; p < p0 + (uint32_t)e; ++p) {
-              const uint32_t m = c.v_meta[p];
-              if (!triggers(m)) continue;
-              const uint32_t e0 = c.row_ptr[c.v_row[p]], e1 = c.row_ptr[c.v_row[p + 1]];
-              const bool cat = (m & VM_CATEGORICAL) != 0;
-              const double kappa = cat ? 0.5 : 0.25;
-              double dot = 0.0;
-              for (uint32_t k = e0; k < e1; ++k) dot += rec_d(k, cat) * x[c.edges[k].wid];
-              for (uint32_t k = e0; k < e1; ++k) {
-                const double d = rec_d(k, cat);
-                if (d == 0.0) continue;
-                __atomic_fetch_add(&yfix[c.edges[k].wid], (long long)std::llrint(scale * (kappa * d * dot)), __ATOMIC_RELAXED);
-                if (iter == 0) __atomic_fetch_add(&dfix[c.edges[k].wid], (long long)std::llrint(dscale * (kappa * d * d)), __ATOMIC_RELAXED);
-              }
-            }
-          }, 0);
-          std::vector<double> part(3 * T, 0.0);
-          parallel_parts(c.W, T, [&](uint32_t t, uint64_t b, uint64_t e) {
-            double xy = 0.0, xx = 0.0, yy = 0.0;
-            for (uint64_t w = b; w < e; ++w) {
-              const double yw = (double)yfix[w] / scale;
-              y[w] = yw;
-              xy += x[w] * yw; xx += x[w] * x[w]; yy += yw * yw;
-            }
-            part[3 * t] = xy; part[3 * t + 1] = xx; part[3 * t + 2] = yy;
-          }, 0);
-          double xy = 0.0, xx = 0.0, yy = 0.0;
-          for (uint32_t t = 0; t < T; ++t) { xy += part[3 * t]; xx += part[3 * t + 1]; yy += part[3 * t + 2]; }
-          if (xx > 0) lam = std::max(lam, xy / xx);
-          const double norm = yy > 0 ? 1.0 / std::sqrt(yy) : 0.0;
-          parallel_ranges(c.W, T, [&](uint64_t b, uint64_t e) { for (uint64_t w = b; w < e; ++w) { x[w] = y[w] * norm; y[w] = 0.0; yfix[w] = 0; } });
-        }
-        std::vector<double> dpart(T, 0.0);
-        parallel_parts(c.W, T, [&](uint32_t t, uint64_t b, uint64_t e) {
-          long long mx = 0;
-          for (uint64_t w = b; w < e; ++w) { mx = std::max(mx, dfix[w]); x[w] = 0.0; }
-          dpart[t] = (double)mx / dscale;
-        }, 0);
-        for (uint32_t t = 0; t < T; ++t) dmax = std::max(dmax, dpart[t]);
-        } else {
-          std::fill(x.begin(), x.end(), 0.0);
-        }
-      } else {
-      for (int iter = 0; iter < 3; ++iter) {
-        for (uint32_t p = p0; p < p1; ++p) {
-          const uint32_t m = c.v_meta[p];
-          if (!triggers(m)) continue;
-          const uint32_t e0 = c.row_ptr[c.v_row[p]], e1 = c.row_ptr[c.v_row[p + 1]];
-          const double kappa = (m & VM_CATEGORICAL) ? 0.5 : 0.25;
-          double dot = 0.0;
-          for (uint32_t e = e0; e < e1; ++e) {
-            const double d = rec_d(e, (m & VM_CATEGORICAL) != 0);
-            if (d == 0.0) continue;
-            const uint32_t w = c.edges[e].wid;
-            if (!seen[w]) { seen[w] = 1; touched.push_back(w); x[w] = 1.0; }
-            dot += d * x[w];
-          }
-          for (uint32_t e = e0; e < e1; ++e) {
-            const double d = rec_d(e, (m & VM_CATEGORICAL) != 0);
-            if (d == 0.0) continue;
-            y[c.edges[e].wid] += kappa * d * dot;
-            if (iter == 0) diag[c.edges[e].wid] += kappa * d * d;   // (lower bound of H_ww)
-          }
-        }
-        double xy = 0.0, xx = 0.0, yy = 0.0;
-        for (uint32_t w : touched) { xy += x[w] * y[w]; xx += x[w] * x[w]; yy += y[w] * y[w]; }
-        if (xx > 0) lam = std::max(lam, xy / xx);
-        const double norm = yy > 0 ? 1.0 / std::sqrt(yy) : 0.0;
-        for (uint32_t w : touched) { x[w] = y[w] * norm; y[w] = 0.0; }
-      }
-      for (uint32_t w : touched) { dmax = std::max(dmax, diag[w]); diag[w] = 0.0; seen[w] = 0; x[w] = 0.0; }
-      touched.clear();
-      }
-      lam_max = std::max(lam_max, 1.1 * std::max(lam, dmax));
+      const double lam = on_device && hostb::batch_is_dense(c, p0, p1)
+          ? devb::batch_curvature(p0, p1, s->d_v_meta, s->d_v_row, s->d_row_ptr, s->d_edges, s->d_edge_fval64,
+                                  s->opts.learn_non_evidence != 0, s->opts.noise_aware != 0, (uint32_t)c.W, dev_sc, (void *)s->stream)
+          : hostb::batch_curvature(c, s->opts, p0, p1, host_sc);
+      lam_max = std::max(lam_max, 1.1 * lam);
     }
   }
   if (getenv("DWX_TIMING")) fprintf(stderr, "[dwx curvature] batches=%u lambda=%.6g\n", batches, lam_max);
@@ -1973,9 +1381,7 @@ int dwx_graph_create(const dwx_graph_desc *desc, const dwx_compile_opts *opts, d
   if (!desc || !out) return fail(DWX_E_INVALID, "null argument");
   dwx_compile_opts o{};
   if (opts) o = *opts;
-  // the weight-sorted copy of the records is built on the sampler's device where the library can
-  // (device_build.hip; DWX_HOST_BUILD=1: the host builder, which is also its checker)
-  o.defer_sorted_records = devb::available() && !getenv("DWX_HOST_BUILD");
+  o.defer_sorted_records = build_on_device();   // (the weight-sorted copy of the records: built by every sampler)
   bool limit = false;
   try {
     auto cg = std::make_shared<CompiledGraph>();

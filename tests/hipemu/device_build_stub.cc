@@ -1,5 +1,5 @@
 // device_build_stub.cc -- TEST-ONLY: the host harness has no device to build on; the host builders
-// of graph_compile.cc / dwx_api.cc run instead (they are also the checker of the device build).
+// of graph_compile.cc / level_build.cc run instead (they are also the checker of the device build).
 #include <stdexcept>
 
 #include "device_build.h"

@@ -130,7 +130,7 @@ def test_device_built_sorted_records_equal_the_host_builder(lib, monkeypatch):
 def test_device_built_static_tables_equal_the_host_builder(lib, monkeypatch):
     """A plan level's static update counts T and curvature bounds h per chunk, built on the device
     (device_build.hip: a lane per variable, integer atomics) against the host builder
-    (DWX_HOST_BUILD=1; dwx_api.cc build_level): the same tables bit for bit -- unary and pairwise
+    (DWX_HOST_BUILD=1; level_build.cc build_static_tables): the same tables bit for bit -- unary and pairwise
     and ternary factors, boolean and categorical variables, fixed weights, several feature values,
     un-split and split levels."""
     rng = np.random.default_rng(9)

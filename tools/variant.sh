@@ -9,7 +9,9 @@ mkdir -p variants
   "$@" -x hip -c -o variants/$name.o dwx_api.cc
 # (the graph compiler shares device_types.h with the kernels: same flags)
 g++ -O2 -std=c++17 -fPIC -Wall -Wextra -pthread "$@" -c -o variants/$name.gc.o graph_compile.cc
+# (the plan-level host builders share device_types.h too, so the defines reach them: the Makefile's flags of level_build.o)
+g++ -O3 -std=c++17 -fPIC -Wall -Wextra -pthread -ffp-contract=off "$@" -c -o variants/$name.lb.o level_build.cc
 make -s device_build.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/$name.so variants/$name.o variants/$name.gc.o device_build.o -pthread
-rm -f variants/$name.o variants/$name.gc.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/$name.so variants/$name.o variants/$name.gc.o variants/$name.lb.o device_build.o -pthread
+rm -f variants/$name.o variants/$name.gc.o variants/$name.lb.o
 echo "built sampler_amd/csrc/variants/$name.so"

@@ -539,7 +539,15 @@ int dwx_stream(dwx_sampler *s, void **stream);
  * time: launches = the weight-sorted super-tiles of learning sweeps that took their potentials from the
  * potential cache instead of streaming their records, sweeps = the learning sweeps that read it, since the
  * sampler was created (all-unary graphs with weight-sorted learning sweeps, an un-split learning sweep right
- * after an inference sweep on the same weights; DWX_NO_POT_CACHE=1 at the first inference sweep disables it). */
+ * after an inference sweep on the same weights; DWX_NO_POT_CACHE=1 at the first inference sweep disables it); 7 = the
+ * deferred draws: ms = device time of the flushes since the last reset, launches = the flushes and
+ * sweeps = the learning sweeps that deferred since the sampler was created.  An un-split learning sweep of an
+ * all-unary graph (learn_non_evidence and noise_aware off) launches over its evidence tiles only; the draws of its
+ * query variables, which nothing reads while sweeps follow each other, are run -- with that sweep's counter and
+ * weights, the same values bit for bit -- only when dwx_get_assignments, dwx_set_assignments, dwx_set_sweep, a halo
+ * exchange or dwx_device_buffer(DWX_BUF_ASSIGN_*) asks before a later sweep has overwritten them.
+ * dwx_device_buffer(DWX_BUF_ASSIGN_*) also ends deferral for the rest of the sampler's life (the caller keeps the
+ * pointer); DWX_NO_DEFER=1 at dwx_sampler_create disables it. */
 int dwx_kernel_time(dwx_sampler *s, int kind, double *ms, uint64_t *launches, uint64_t *sweeps);
 int dwx_kernel_time_reset(dwx_sampler *s, int enable);
 

@@ -186,6 +186,9 @@ constexpr uint32_t OPT_HAS_TRUTHINESS = 1u << 4;
 // gradient does not apply (scatter the gradient instead).
 constexpr uint32_t OPT_DYNAMIC_T = 1u << 5;
 constexpr uint32_t OPT_NO_PULL = 1u << 6;
+// A learning launch that redraws deferred query variables after an inference sweep has already
+// rewritten their evidence chain: it stores the free chain only.
+constexpr uint32_t OPT_FREE_CHAIN_ONLY = 1u << 7;
 
 constexpr double FIX_SCALE = 1073741824.0;  // 2^30: gradient fixed-point scale
 // Per-weight curvature bounds h[w] (apply_kernel's saturating step) are summed in fixed point

@@ -450,6 +450,8 @@ void Rank::halo(int chains) {
     return nb;
   };
   std::vector<Xfer> sends, recvs;
+  // (the chains are touched through dwx_halo_pack_async / dwx_halo_unpack_async only, which draw what a learning
+  // sweep deferred first -- DESIGN.md 3.1i; nothing else in this file or in dw_cli.cc reads or writes them)
   for (auto &p : send_) { ok(dwx_halo_pack_async(p.h, chains)); sends.push_back({p.peer, p.buf, bytes(p)}); }
   for (auto &p : recv_) recvs.push_back({p.peer, p.buf, bytes(p)});
   sh_.comm->exchange(rank_, s_, sends, recvs);    // (every rank takes part, also with empty lists)

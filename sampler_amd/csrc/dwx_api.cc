@@ -248,6 +248,18 @@ struct dwx_sampler {
   bool last_infer = false;          // the last sweep enqueued was an inference sweep
   bool pot_query_first = false;     // DWX_POT_QUERY_FIRST: a learning launch runs its cached super-tiles first (A/B)
   uint64_t pot_supers = 0, pot_sweeps = 0;   // super-tiles / learning sweeps served from the cache
+  // Deferred draws: an un-split learning sweep of an all-unary graph launches over its
+  // evidence tiles only; the draws of its query tiles are owed until somebody reads the chains
+  // (flush_pending) or a later sweep overwrites them unread (drop_pending / enqueue_inference).
+  struct Pending {
+    bool owed = false;            // the free chain of every query variable is still that of an earlier sweep
+    bool evid_owed = false;       // ... and so is the evidence chain (no inference sweep has run since)
+    uint64_t sweep = 0;           // the sweep counter the owed draws are drawn with
+    std::vector<uint8_t> cached;  // [launches] the potential cache still holds that launch's sums under the sweep's weights
+  } pending;
+  bool defer_ok = false;          // the graph and the options allow it, and no assignment buffer was handed out
+  float *d_w32_prev = nullptr;    // [W + 1] d_w32 as the last deferring sweep read it (allocated by the first one)
+  uint64_t deferred_sweeps = 0, flushes = 0;
   bool has_simple_tiles = false;
   // pull-based gradient (TILE_PULL tiles)
   unsigned long long *d_delta = nullptr;
@@ -335,8 +347,8 @@ struct dwx_sampler {
   bool timing = false;
   uint64_t graph_launches = 0;        // split learning sweeps handed over as one graph launch
   std::vector<TimedSpan> spans;
-  double t_ms[3] = {0, 0, 0};   // [0] inference sweep kernels, [1] learning sweep kernels, [2] pull_grad
-  uint64_t t_launches[3] = {0, 0, 0}, t_sweeps[3] = {0, 0, 0};
+  double t_ms[4] = {0, 0, 0, 0};   // [0] inference sweep kernels, [1] learning sweep kernels, [2] pull_grad, [3] flushes of deferred draws
+  uint64_t t_launches[4] = {0, 0, 0, 0}, t_sweeps[4] = {0, 0, 0, 0};
 
   ~dwx_sampler() {
     for (auto &sp : spans) { rt::event_destroy(sp.a); rt::event_destroy(sp.b); rt::event_destroy(sp.c); }
@@ -347,7 +359,7 @@ struct dwx_sampler {
     rt::dfree(d_grad32); rt::dfree(d_pack_bad);
     rt::dfree(d_edges); rt::dfree(d_edges8); rt::dfree(d_vifs); rt::dfree(d_assign_free); rt::dfree(d_assign_evid);
     rt::dfree(d_tally); rt::dfree(d_weights); rt::dfree(d_w32); rt::dfree(d_w_init); rt::dfree(d_terms); rt::dfree(d_delta);
-    rt::dfree(d_pot); rt::dfree(d_rb); rt::dfree(d_trace);
+    rt::dfree(d_pot); rt::dfree(d_rb); rt::dfree(d_trace); rt::dfree(d_w32_prev);
     rt::dfree(d_w_fixed); rt::dfree(d_grad); rt::dfree(d_persist_rows); rt::dfree(d_persist_bar);
     rt::dfree(d_gbuf[1]); rt::dfree(d_gbuf[2]); rt::dfree(d_wbuf64[0]); rt::dfree(d_wbuf64[1]); rt::dfree(d_wbuf32[0]); rt::dfree(d_wbuf32[1]);
     for (int i = 0; i < 2; ++i) { if (side[i]) rt::stream_destroy(side[i]); if (ev_join[i]) rt::event_destroy(ev_join[i]); }
@@ -432,9 +444,10 @@ void resolve_builds(dwx_sampler *s, size_t lds_infer, size_t lds_learn, size_t l
 // covered (if given): the end of the gap-free run of weight-sorted super-tiles that starts at t0 (t0: none)
 // P.rb (inference only): the builds that add every draw's conditional to it (dwx_rb_enable)
 // P.trace (multi only): the builds that write every sweep's draws to the sample trace (dwx_trace_enable)
+// default_layout (learning): never the plan level's own super-tiles -- a launch over one side of the query end
 template <bool LEARN>
 uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, uint32_t t1, const bool multi = false,
-                      uint32_t *covered = nullptr) {
+                      uint32_t *covered = nullptr, const bool default_layout = false) {
   if (LEARN && (P.rb || multi)) throw std::logic_error("Rao-Blackwellised sums, several sweeps per launch: inference sweeps only");
   const bool rb = P.rb != nullptr, trace = multi && P.trace != nullptr;
   // (no learning kernel has an RB build: a learning launch names its plain build both times)
@@ -489,7 +502,8 @@ uint32_t launch_tiles(dwx_sampler *s, KernelParams &P, size_t l, uint32_t t0, ui
   if (s->d_supers && !P.edge_terms && !multi && (!LEARN || (s->sorted_learn && !(P.flags & (OPT_NO_PULL | OPT_DYNAMIC_T))))) {
     // (a chunk of a split learning sweep: the plan level's own layout, cut along the chunks; a learning
     // launch on the potential cache: the default layout, whose super-tiles end at the query tiles' end)
-    const dwx_sampler::Level *lv = (LEARN && !P.pot && s->plan_level && s->plan_level->d_supers) ? s->plan_level : nullptr;
+    const dwx_sampler::Level *lv =
+        (LEARN && !P.pot && !default_layout && s->plan_level && s->plan_level->d_supers) ? s->plan_level : nullptr;
     const std::vector<SuperTile> &sv = lv ? lv->sorted_supers : c.supers;
     const SuperTile *d_sv = lv ? lv->d_supers : s->d_supers;
     const SortRec8 *d_sr = lv ? lv->d_sorted : s->d_sorted;
@@ -594,8 +608,12 @@ bool multi_sweep_graph(const dwx_sampler *s) {
 // Sample trace: pack the inference chain's current assignment into n_planes planes of the ring from trace_next on
 // (unsampled_only: only the positions inference sweeps do not draw, the others cleared -- the planes a one-launch
 // run is about to fill), and enter sweeps [first_id, first_id + n_planes) as the ring's newest entries.
+void flush_pending(dwx_sampler *s, int chains = 3);
 void trace_pack(dwx_sampler *s, uint64_t first_id, uint32_t n_planes, bool unsampled_only) {
   const CompiledGraph &c = *s->cg;
+  // (deferred draws: the callers pack behind an inference sweep, which has rewritten the evidence chain of every
+  // query variable, or the unsampled positions only -- neither reads an owed value; any other use flushes)
+  if (!unsampled_only) flush_pending(s, 2);
   const uint32_t n = (uint32_t)c.Vo;
   if (n) {
     const uint32_t items = s->trace_bits == 1 ? n : (n + 3u) / 4u;
@@ -633,6 +651,39 @@ void span_end(dwx_sampler *s, TimedSpan &sp, uint32_t launches, bool has_pull, b
   s->spans.push_back(sp);
 }
 
+// Deferred draws.  The query draws a learning sweep left out, run now if a chain in `chains`
+// (bit 0 free, bit 1 evidence) still holds an earlier sweep's values: the learning kernels over the query tiles of
+// every colour launch, with the sweep counter and the weights of that sweep -- the potential cache where it still
+// holds the sums those weights give, else the records streamed against the snapshot of d_w32 -- and no gradient
+// work (query variables trigger none).  Every reader and writer of the two arrays calls this first.
+void flush_pending(dwx_sampler *s, int chains) {
+  dwx_sampler::Pending &pd = s->pending;
+  if (!(((pd.owed ? 1 : 0) | (pd.evid_owed ? 2 : 0)) & chains)) return;
+  rt::set_device(s->device);
+  const CompiledGraph &c = *s->cg;
+  KernelParams P = s->base;
+  P.sweep = pd.sweep;
+  P.w32 = s->d_w32_prev;
+  if (!pd.evid_owed) P.flags |= OPT_FREE_CHAIN_ONLY;   // (an inference sweep has drawn that chain since)
+  TimedSpan sp = span_begin(s, 3);
+  uint32_t launches = 0;
+  for (size_t l = 0; l + 1 < c.launch_off.size(); ++l) {
+    KernelParams Q = P;
+    if (l < pd.cached.size() && pd.cached[l]) {
+      Q.pot = s->d_pot;
+      Q.pot_v0 = c.tile_v[c.launch_tile[l]];
+      Q.pot_v1 = c.tile_v[c.launch_query_tile_end[l]];
+    }
+    launches += launch_tiles<true>(s, Q, l, c.launch_tile[l], c.launch_query_tile_end[l], false, nullptr, true);
+  }
+  span_end(s, sp, launches, false, false);
+  pd.owed = pd.evid_owed = false;
+  ++s->flushes;
+}
+
+// a learning sweep draws (or defers) both chains of every query variable itself: nothing older is owed
+void drop_pending(dwx_sampler *s) { s->pending.owed = s->pending.evid_owed = false; }
+
 void enqueue_inference_multi(dwx_sampler *s, uint32_t n) {
   const CompiledGraph &c = *s->cg;
   rt::set_device(s->device);
@@ -641,6 +692,7 @@ void enqueue_inference_multi(dwx_sampler *s, uint32_t n) {
   P.n_sweeps = n;
   P.edge_terms = nullptr;
   P.rb = s->rb_on ? s->d_rb : nullptr;
+  s->pending.evid_owed = false;   // (deferred draws: these sweeps overwrite every query variable's evidence chain)
   TimedSpan sp = span_begin(s, 0);
   uint32_t launches = 0;
   // the sample trace: the last min(n, capacity) sweeps of the launch write their planes themselves
@@ -710,6 +762,10 @@ void enqueue_inference(dwx_sampler *s) {
   // the potential cache is stored once a learning sweep is known to follow inference sweeps (on a
   // sampler that only infers, it would be bandwidth spent for nothing -- the rule of the terms table)
   P.pot = (s->pot_wanted && !P.edge_terms && pot_cache_ready(s)) ? s->d_pot : nullptr;
+  // deferred draws: this sweep overwrites the evidence chain of every query variable, and where it stores into
+  // the potential cache, the sums an owed draw would have read
+  s->pending.evid_owed = false;
+  if (P.pot) std::fill(s->pending.cached.begin(), s->pending.cached.end(), (uint8_t)0);
   TimedSpan sp = span_begin(s, 0);
   uint32_t launches = 0;
   for (size_t l = 0; l + 1 < c.launch_off.size(); ++l) {
@@ -739,6 +795,10 @@ void enqueue_inference(dwx_sampler *s) {
 // and a second copy of the records: dwx_options.plan_layouts says when it is built.
 void ensure_level_layout(dwx_sampler *s, dwx_sampler::Level *L, uint32_t batches) {
   if (L->layout_done) return;
+  // (deferred draws: an un-split sweep launches over the evidence tiles alone, which the default layout serves
+  // whole -- no layout unless the caller asked for one with the level, plan_layouts == 1; not marked done: a sampler
+  // whose deferral ends wants it after all)
+  if (batches == 1 && s->defer_ok && s->opts.plan_layouts != 1) return;
   L->layout_done = true;
   const CompiledGraph &c = *s->cg;
   bool mixed_launch = false;
@@ -1099,15 +1159,39 @@ void enqueue_learn_chunk(dwx_sampler *s, uint32_t chunk) {
     s->last_infer = false;
   }
   const uint32_t l = ch.launch;
-  if (!split && s->pot_alloc > 0 && l < s->pot_valid.size() && s->pot_valid[l]) {
-    const CompiledGraph &c = *s->cg;
-    P.pot = s->d_pot;
-    P.pot_v0 = c.tile_v[c.launch_tile[l]];
-    P.pot_v1 = c.tile_v[c.launch_query_tile_end[l]];
+  const CompiledGraph &c = *s->cg;
+  const bool pot_hit = !split && s->pot_alloc > 0 && l < s->pot_valid.size() && s->pot_valid[l];
+  // Deferred draws: an un-split sweep of an all-unary graph draws its evidence tiles only.
+  // Nothing reads a query variable's two values while sweeps follow each other, so its draws are owed --
+  // with this sweep's counter, d_w32 as it stands before the update (the snapshot) and, for now, the
+  // potential cache -- until a reader asks (flush_pending) or a later sweep overwrites them unread.
+  const bool defer = s->defer_ok && !split;
+  dwx_sampler::Pending &pd = s->pending;
+  if (chunk == 0 || !defer || pd.sweep != s->sweep) drop_pending(s);
+  if (defer) {
+    if (!pd.owed) {
+      const size_t w32_bytes = ((size_t)c.W + 1) * sizeof(float);
+      if (!s->d_w32_prev) s->d_w32_prev = (float *)rt::dmalloc(w32_bytes);
+      rt::d2d(s->d_w32_prev, s->d_w32, w32_bytes, s->stream);
+      pd.owed = pd.evid_owed = true;
+      pd.sweep = s->sweep;
+      pd.cached.assign(c.launch_tile.size(), 0);
+      ++s->deferred_sweeps;
+    }
+    pd.cached[l] = pot_hit ? 1 : 0;
+  }
+  if (pot_hit) {
+    // (a deferring launch has no query tile to read the cache: it is counted as the sweep that would have)
+    if (!defer) {
+      P.pot = s->d_pot;
+      P.pot_v0 = c.tile_v[c.launch_tile[l]];
+      P.pot_v1 = c.tile_v[c.launch_query_tile_end[l]];
+    }
     if (chunk == 0) ++s->pot_sweeps;
   }
   TimedSpan sp = span_begin(s, 1);
-  const uint32_t launches = launch_tiles<true>(s, P, ch.launch, ch.t0, ch.t1);
+  const uint32_t launches = defer ? launch_tiles<true>(s, P, l, std::max(ch.t0, c.launch_query_tile_end[l]), ch.t1, false, nullptr, true)
+                                  : launch_tiles<true>(s, P, l, ch.t0, ch.t1);
   if (s->timing) rt::event_record(sp.b, s->stream);
   bool pulled = false;
   // the pull-based gradient of the TILE_PULL tiles: un-split sweeps once, after the last
@@ -1224,6 +1308,7 @@ bool enqueue_merged_sweep(dwx_sampler *s) {
     for (int k = 0; k < 2; ++k) { s->d_wbuf64[k] = (double *)rt::dmalloc((size_t)W * 8); s->d_wbuf32[k] = (float *)rt::dmalloc((size_t)W * 4 + 4); }
   }
   s->d_gbuf[0] = s->d_grad;
+  drop_pending(s);   // (a split sweep draws every variable's two chains)
   if (s->plan_level) ++s->plan_level->sweeps;
   const unsigned cap = s->kv.learn.cap;
   // The leading tiles of the first mini-batch in which NOTHING learns -- the query part of the colour launch:
@@ -1319,6 +1404,7 @@ bool enqueue_persistent_sweep(dwx_sampler *s) {
     rt::stream_sync(s->stream);      // (the host copy dies with this scope)
   }
   ++L->sweeps;
+  drop_pending(s);   // (a split sweep draws every variable's two chains)
   KernelParams P = s->base;
   P.sweep = s->sweep;
   PersistArgs A{};
@@ -1533,6 +1619,8 @@ int dwx_sampler_create(const dwx_graph *g, const dwx_options *opts, dwx_sampler 
     s->d_edges = upload(c.edges, st, 1);
     s->rec8 = c.edges8.size() != 0;
     if (s->rec8) s->d_edges8 = upload(c.edges8, st, 1);
+    // deferred draws: all-unary graphs on which a query variable triggers no SGD (DWX_NO_DEFER: A/B knob)
+    s->defer_ok = s->rec8 && !opts->learn_non_evidence && !opts->noise_aware && !getenv("DWX_NO_DEFER");
     if (!c.supers.empty()) {
       s->d_supers = upload(c.supers, st);
       if (c.sorted_deferred) {
@@ -2372,6 +2460,7 @@ int dwx_get_assignments(dwx_sampler *s, int chain, uint64_t *out) {
   return guarded([&]() {
     const CompiledGraph &c = *s->cg;
     rt::set_device(s->device);
+    flush_pending(s, chain == 0 ? 1 : 2);
     std::vector<uint32_t> a(c.V);
     rt::d2h(a.data(), chain == 0 ? s->d_assign_free : s->d_assign_evid, c.V * 4, s->stream);
     rt::stream_sync(s->stream);
@@ -2384,6 +2473,7 @@ int dwx_set_assignments(dwx_sampler *s, int chain, const uint64_t *in) {
   return guarded([&]() {
     const CompiledGraph &c = *s->cg;
     rt::set_device(s->device);
+    flush_pending(s);   // (owed draws must not land on top of the caller's values)
     std::vector<uint32_t> a(c.V);
     for (uint64_t p = 0; p < c.V; ++p) a[p] = (uint32_t)in[c.perm[p]];
     rt::h2d(chain == 0 ? s->d_assign_free : s->d_assign_evid, a.data(), c.V * 4, s->stream);
@@ -2399,13 +2489,29 @@ int dwx_get_sweep(dwx_sampler *s, uint64_t *out) {
 
 int dwx_set_sweep(dwx_sampler *s, uint64_t sweep) {
   if (!s) return fail(DWX_E_INVALID, "null sampler");
-  s->sweep = sweep;
-  return DWX_OK;
+  // (owed draws carry their own counter; flushed all the same, so that a counter set back meets no older record)
+  return guarded([&]() {
+    flush_pending(s);
+    s->sweep = sweep;
+  });
 }
 
 int dwx_device_buffer(dwx_sampler *s, int which, void **dev_ptr, uint64_t *nbytes) {
   if (!s || !dev_ptr || !nbytes) return fail(DWX_E_INVALID, "null argument");
   const CompiledGraph &c = *s->cg;
+  if (which == DWX_BUF_ASSIGN_FREE || which == DWX_BUF_ASSIGN_EVID) {
+    // the caller keeps the pointer and reads or writes behind the library's back: what is owed is drawn now, and
+    // no learning sweep of this sampler defers again (an un-split level then wants the layout it went without)
+    int rc = guarded([&]() {
+      flush_pending(s);
+      if (!s->defer_ok) return;
+      s->defer_ok = false;
+      auto it = s->levels.find(1);
+      if (it != s->levels.end() && s->opts.plan_layouts == 0 && (build_on_device() || it->second->sweeps >= layout_after_sweeps()))
+        ensure_level_layout(s, it->second.get(), 1);
+    });
+    if (rc != DWX_OK) return rc;
+  }
   switch (which) {
     case DWX_BUF_WEIGHTS: *dev_ptr = s->d_weights; *nbytes = c.W * 8; break;
     case DWX_BUF_GRAD: *dev_ptr = s->d_grad; *nbytes = c.W * 16; break;
@@ -2498,6 +2604,7 @@ int halo_move(dwx_halo *h, int chains, bool pack) {
   return guarded([&]() {
     dwx_sampler *s = h->s;
     rt::set_device(s->device);
+    flush_pending(s);   // (packing reads the chains; owed draws must not land on top of unpacked values)
     const unsigned grid = std::min<unsigned>((h->n + BLOCK_THREADS - 1) / BLOCK_THREADS, 4096u);
     auto go = [&](auto pk, auto unpk) {
       if (pack)
@@ -2529,13 +2636,22 @@ int dwx_kernel_time_reset(dwx_sampler *s, int enable) {
   return guarded([&]() {
     rt::set_device(s->device);
     drain_spans(s);
-    for (int k = 0; k < 3; ++k) { s->t_ms[k] = 0; s->t_launches[k] = 0; s->t_sweeps[k] = 0; }
+    for (int k = 0; k < 4; ++k) { s->t_ms[k] = 0; s->t_launches[k] = 0; s->t_sweeps[k] = 0; }
     s->timing = enable != 0;
   });
 }
 
 int dwx_kernel_time(dwx_sampler *s, int kind, double *ms, uint64_t *launches, uint64_t *sweeps) {
-  if (!s || kind < 0 || kind > 6) return fail(DWX_E_INVALID, "bad argument");
+  if (!s || kind < 0 || kind > 7) return fail(DWX_E_INVALID, "bad argument");
+  if (kind == 7) {   // deferred draws: device time of the flushes since the last reset; flushes and deferring sweeps since create
+    return guarded([&]() {
+      rt::set_device(s->device);
+      drain_spans(s);
+      if (ms) *ms = s->t_ms[3];
+      if (launches) *launches = s->flushes;
+      if (sweeps) *sweeps = s->deferred_sweeps;
+    });
+  }
   if (kind == 6) {   // learning sweeps (and their super-tiles) that took sums from the potential cache
     if (ms) *ms = 0.0;
     if (launches) *launches = s->pot_supers;

@@ -1201,7 +1201,10 @@ DWX_DEV int process_variable(const KernelParams &P, const TileView &T, uint32_t 
   } else {
     p_evid = cat_draw<WMODE, SIMPLE>(P, T, row0, card, P.assign_evid, p, B);
   }
-  if (SIMPLE) DWX_NT_STORE(p_evid, &P.assign_evid[p]); else if (leader) P.assign_evid[p] = p_evid;
+  // (OPT_FREE_CHAIN_ONLY, uniform: a flush of deferred draws behind an inference sweep keeps that sweep's value)
+  if (!(P.flags & OPT_FREE_CHAIN_ONLY)) {
+    if (SIMPLE) DWX_NT_STORE(p_evid, &P.assign_evid[p]); else if (leader) P.assign_evid[p] = p_evid;
+  }
   // src/gibbs_sampler.h:144-146
   if (!(P.flags & OPT_LEARN_NON_EVIDENCE) &&
       ((!noise_aware && !is_evid) || (noise_aware && !has_truth)))
@@ -1275,7 +1278,7 @@ DWX_DEV int learn_variable_terms2(const KernelParams &P, const uint32_t *rowptr,
   const uint32_t evid_value = pre.init;
   // boolean variables carry no truthiness: sample_evid is "evidence value" or a Gibbs draw
   const uint32_t p_evid = (!noise_aware && is_evid) ? evid_value : bool_draw(B, ppe, pne);
-  P.assign_evid[p] = p_evid;
+  if (!(P.flags & OPT_FREE_CHAIN_ONLY)) P.assign_evid[p] = p_evid;
   if (!(P.flags & OPT_LEARN_NON_EVIDENCE) && (noise_aware || !is_evid)) return 0;
   for (uint32_t e = es; e < ee; ++e) {
     const Rec r = recs[e - edge_bias];
@@ -1327,7 +1330,7 @@ DWX_DEV int learn_variable_terms2_pair(const KernelParams &P, const uint32_t *ro
     P.assign_free[p] = mine;
   } else {
     mine = (!noise_aware && is_evid) ? evid_value : bool_draw(B, pp, pn);
-    P.assign_evid[p] = mine;
+    if (!(P.flags & OPT_FREE_CHAIN_ONLY)) P.assign_evid[p] = mine;
   }
   const uint32_t theirs = DWX_PAIR_SWAP_U32(mine);
   const uint32_t p_free = chain == 0u ? mine : theirs;

@@ -98,8 +98,10 @@ typedef struct dwx_compile_opts {
   uint32_t no_sorted_records;  /* 1: no weight-sorted second copy of the records of boolean all-unary
                                   tiles (default 0: compact-record graphs with >= 4096 weights get
                                   one, and their sweeps gather weights in sorted order)        */
-  uint32_t super_tiles;        /* tiles per weight-sorted super-tile, at most (default 64 = 16 384 variables:
-                                  128 KiB of fixed-point sums, the CU's LDS)                            */
+  uint32_t super_tiles;        /* tiles per weight-sorted super-tile, at most (default 75 to 79 = 19 200 to
+                                  20 224 variables: the fixed-point sums that fit the CU's 160 KiB of LDS
+                                  beside the graph's table of distinct record values; more tiles than
+                                  that only where tiles are smaller than 256 variables)                  */
   uint32_t sorted_slots;       /* workgroups of sorted_sweep_kernel resident at once (default 256: one
                                   1024-thread workgroup per CU of an MI355X); runs of tiles are cut into
                                   multiples of it                                                       */
@@ -138,6 +140,7 @@ typedef struct dwx_graph_info {
    * 32-bit counts (G >> grad_shift) while ranks x max_records_per_weight x grad_unit_max < 2^31.
    * grad_shift == 0: nothing is known (categorical variables, non-unary factors): send int64. */
   uint64_t grad_shift, grad_unit_max, max_records_per_weight;
+  uint64_t max_super_tile_variables; /* variables of the largest weight-sorted super-tile (0: no sorted copy) */
 } dwx_graph_info;
 
 /* Runtime options of one sampler (the CmdParser fields the hot path reads:

@@ -393,12 +393,16 @@ DWX_DEV void apply_one(double *weights, float *w32, const uint8_t *w_fixed, cons
 // w_in (the last update of a sweep whose mini-batches ran as merged launches, persist_kernels.h): the
 // weights before this update live in another buffer -- every weight is written, touched or not;
 // also_zero: a second gradient buffer to clear (the one the last merged launch read).
+// w32_prev (the update after a sweep that deferred draws): every weight's f32 value as that sweep
+// read it is saved there before the new one is written -- all W of them, touched or not.
 __global__ void __launch_bounds__(BLOCK_THREADS)
 apply_kernel(double *weights, float *w32, const uint8_t *w_fixed, long long *grad,
              const long long *t_static, const long long *t_hess, uint32_t W, double stepsize,
-             double reg_param, int l2, const double *w_in = nullptr, long long *also_zero = nullptr) {
+             double reg_param, int l2, const double *w_in = nullptr, long long *also_zero = nullptr,
+             float *w32_prev = nullptr) {
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < W; i += stride) {
+    if (w32_prev) w32_prev[i] = w32[i];
     const long long G = grad[i], Td = grad[W + i];
     if (G != 0 || Td != 0) { grad[i] = 0; grad[W + i] = 0; }
     if (also_zero) { also_zero[i] = 0; also_zero[W + i] = 0; }

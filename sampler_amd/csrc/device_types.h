@@ -73,21 +73,36 @@ constexpr uint32_t REC8_FIXED = 1u << 27, REC8_HIT_SHIFT = 28, REC8_MISS_SHIFT =
 // -- neighbouring lanes of the record stream then gather neighbouring weights: a fraction of an
 // L2 request per record instead of one.  A record adds w * d to its owner's potential
 // difference pp - pn, d = (sign(hit) - sign(miss)) * f, summed in fixed point in LDS (pot_fix).
-//   wid: the weight id;  od: bits 0-13 (SORT_OWNER_BITS) the owner's slot in the super-tile (variable
-//   position - SuperTile::v0), bits 14-31 the index of d in the table of distinct values (entry 0 is
+//   wid: the weight id;  od: bits 0-14 (SORT_OWNER_BITS) the owner's slot in the super-tile (variable
+//   position - SuperTile::v0), bits 15-31 the index of d in the table of distinct values (entry 0 is
 //   0.0: the zero-filled lanes past a super-tile's end add nothing).
 struct alignas(8) SortRec8 {
   uint32_t wid, od;
 };
 static_assert(sizeof(SortRec8) == 8, "SortRec8 must be 8 bytes");
 #ifndef DWX_SORT_OWNER_BITS
-#define DWX_SORT_OWNER_BITS 14
+#define DWX_SORT_OWNER_BITS 15
 #endif
 constexpr uint32_t SORT_OWNER_BITS = DWX_SORT_OWNER_BITS, SORT_OWNER_MASK = (1u << SORT_OWNER_BITS) - 1;
-constexpr uint32_t SUPER_NV_MAX = 1u << SORT_OWNER_BITS;      // 16 384 variables: 128 KiB of fixed-point sums
-constexpr uint32_t SUPER_TILES_DEFAULT = SUPER_NV_MAX / 256;  // 64 full tiles
-constexpr uint32_t SORT_WG_PER_CU = SORT_OWNER_BITS <= 13 ? 2 : 1;   // (14 bits: the CU's whole LDS, one 1024-thread workgroup per CU)
-constexpr uint32_t SORT_TV_SLOTS = 2 * SUPER_TILES_DEFAULT;   // tile starts of a super-tile in LDS (+ end), padded
+constexpr uint32_t SORT_WG_PER_CU = SORT_OWNER_BITS <= 13 ? 2 : 1;   // (14 bits and up: the CU's whole LDS, one 1024-thread workgroup per CU)
+constexpr uint32_t SORT_TV_SLOTS = 128;                       // tile starts of a super-tile in LDS (+ end), padded
+constexpr uint32_t SORT_MAX_DVALS = 1024;                     // distinct d values (8 KiB in LDS), else no sorted copy
+// sorted_sweep_kernel's dynamic LDS: the tile starts, the table of distinct d (n_dvals entries, entry 0 included),
+// then one 8-byte fixed-point sum per variable of the super-tile -- as many as the CU's 160 KiB leave room for
+constexpr uint32_t SORT_LDS_BYTES = 160u * 1024u;
+constexpr uint32_t sort_acc_offset(uint32_t n_dvals) { return SORT_TV_SLOTS * 4u + n_dvals * 8u; }
+// The largest super-tile, in variables: what fits those sums, in whole tiles of 256 variables (20 224 = 79 tiles
+// beside a table of two d values, 19 200 = 75 tiles beside a full one), and what the owner field can name (14-bit
+// A/B build: 16 384).  The ONE place that decides it: the host layout builder, the device builder (through the host's
+// plan) and the launch code all ask here.
+constexpr uint32_t super_nv_cap(uint32_t n_dvals) {
+  const uint32_t fit = (SORT_LDS_BYTES - sort_acc_offset(n_dvals)) / 8u / 256u * 256u;
+  return fit < (1u << SORT_OWNER_BITS) ? fit : (1u << SORT_OWNER_BITS);
+}
+constexpr uint32_t sort_lds_bytes(uint32_t n_dvals) { return sort_acc_offset(n_dvals) + super_nv_cap(n_dvals) * 8u; }
+constexpr uint32_t super_tiles_default(uint32_t n_dvals) { return super_nv_cap(n_dvals) / 256u; }   // full tiles per super-tile
+static_assert(super_nv_cap(SORT_MAX_DVALS) >= 256u && sort_lds_bytes(SORT_MAX_DVALS) <= SORT_LDS_BYTES &&
+              sort_lds_bytes(2) <= SORT_LDS_BYTES && super_tiles_default(2) < SORT_TV_SLOTS, "sorted_sweep_kernel's LDS");
 #ifndef DWX_SORT_THREADS
 #define DWX_SORT_THREADS 1024
 #endif
@@ -98,10 +113,9 @@ constexpr uint32_t SORT_THREADS = DWX_SORT_THREADS;   // sorted_sweep_kernel's w
 constexpr int SORT_K = DWX_SORT_K;                    // ... and its records in flight per lane
 // persist_learn8_kernel: every workgroup adds up all workgroups' gradient rows itself -- few weights only
 constexpr uint32_t PERSIST_MAX_W = 128;
-constexpr uint32_t SORT_MAX_DVALS = 1024;                     // distinct d values (8 KiB in LDS), else no sorted copy
 struct alignas(16) SuperTile {
   uint32_t tile0, ntiles;   // tiles [tile0, tile0 + ntiles)
-  uint32_t v0, nv;          // variables [v0, v0 + nv), nv <= SUPER_NV_MAX
+  uint32_t v0, nv;          // variables [v0, v0 + nv), nv <= super_nv_cap(n_dvals)
   uint32_t lo, hi;          // sorted records [lo | hi << 32, ... + nrec)
   uint32_t nrec, pad;
 };

@@ -255,10 +255,12 @@ struct dwx_sampler {
     bool owed = false;            // the free chain of every query variable is still that of an earlier sweep
     bool evid_owed = false;       // ... and so is the evidence chain (no inference sweep has run since)
     uint64_t sweep = 0;           // the sweep counter the owed draws are drawn with
+    bool snap = false;            // d_w32 has changed since that sweep: its weights are in d_w32_prev (else still in d_w32)
     std::vector<uint8_t> cached;  // [launches] the potential cache still holds that launch's sums under the sweep's weights
   } pending;
   bool defer_ok = false;          // the graph and the options allow it, and no assignment buffer was handed out
-  float *d_w32_prev = nullptr;    // [W + 1] d_w32 as the last deferring sweep read it (allocated by the first one)
+  float *d_w32_prev = nullptr;    // [W + 1] d_w32 as the last deferring sweep read it, once pending.snap says so: written
+                                  // by whoever overwrites d_w32 first (apply_kernel; keep_snapshot for the host's writers)
   uint64_t deferred_sweeps = 0, flushes = 0;
   bool has_simple_tiles = false;
   // pull-based gradient (TILE_PULL tiles)
@@ -663,7 +665,7 @@ void flush_pending(dwx_sampler *s, int chains) {
   const CompiledGraph &c = *s->cg;
   KernelParams P = s->base;
   P.sweep = pd.sweep;
-  P.w32 = s->d_w32_prev;
+  P.w32 = pd.snap ? s->d_w32_prev : s->d_w32;
   if (!pd.evid_owed) P.flags |= OPT_FREE_CHAIN_ONLY;   // (an inference sweep has drawn that chain since)
   TimedSpan sp = span_begin(s, 3);
   uint32_t launches = 0;
@@ -683,6 +685,15 @@ void flush_pending(dwx_sampler *s, int chains) {
 
 // a learning sweep draws (or defers) both chains of every query variable itself: nothing older is owed
 void drop_pending(dwx_sampler *s) { s->pending.owed = s->pending.evid_owed = false; }
+
+// d_w32 is about to be rewritten by something other than apply_kernel (which saves the old values itself): if draws
+// are owed under the weights it holds now, they move to d_w32_prev first
+void keep_snapshot(dwx_sampler *s) {
+  dwx_sampler::Pending &pd = s->pending;
+  if (!pd.owed || pd.snap) return;
+  rt::d2d(s->d_w32_prev, s->d_w32, ((size_t)s->cg->W + 1) * sizeof(float), s->stream);
+  pd.snap = true;
+}
 
 void enqueue_inference_multi(dwx_sampler *s, uint32_t n) {
   const CompiledGraph &c = *s->cg;
@@ -1170,10 +1181,15 @@ void enqueue_learn_chunk(dwx_sampler *s, uint32_t chunk) {
   if (chunk == 0 || !defer || pd.sweep != s->sweep) drop_pending(s);
   if (defer) {
     if (!pd.owed) {
-      const size_t w32_bytes = ((size_t)c.W + 1) * sizeof(float);
-      if (!s->d_w32_prev) s->d_w32_prev = (float *)rt::dmalloc(w32_bytes);
-      rt::d2d(s->d_w32_prev, s->d_w32, w32_bytes, s->stream);
+      // (no copy of d_w32 here: the update that follows saves the old values as it overwrites them -- enqueue_apply;
+      // the one copy at allocation defines the padding entry behind the W weights, which nothing rewrites)
+      if (!s->d_w32_prev) {
+        const size_t w32_bytes = ((size_t)c.W + 1) * sizeof(float);
+        s->d_w32_prev = (float *)rt::dmalloc(w32_bytes);
+        rt::d2d(s->d_w32_prev, s->d_w32, w32_bytes, s->stream);
+      }
       pd.owed = pd.evid_owed = true;
+      pd.snap = false;
       pd.sweep = s->sweep;
       pd.cached.assign(c.launch_tile.size(), 0);
       ++s->deferred_sweeps;
@@ -1283,9 +1299,13 @@ void enqueue_apply(dwx_sampler *s) {
     auto it = s->levels.find(1);
     if (it != s->levels.end() && it->second->d_t_static) hs = it->second->d_t_static + W;
   }
+  // draws owed under the weights this update overwrites: the kernel saves them on its way
+  dwx_sampler::Pending &pd = s->pending;
+  float *prev = pd.owed && !pd.snap ? s->d_w32_prev : nullptr;
+  if (prev) pd.snap = true;
   rt::launch(apply_kernel, grid, BLOCK_THREADS, 0, s->stream, s->d_weights, s->d_w32,
              (const uint8_t *)s->d_w_fixed, s->d_grad, ts, hs, W, s->plan_eta, s->opts.reg_param,
-             (int)(s->opts.regularization == 1), (const double *)nullptr, (long long *)nullptr);
+             (int)(s->opts.regularization == 1), (const double *)nullptr, (long long *)nullptr, prev);
 }
 
 // A split learning sweep of an all-unary graph with few weights (LDS gradient accumulators), one launch
@@ -1377,7 +1397,7 @@ bool enqueue_merged_sweep(dwx_sampler *s) {
     const double *w_in = last == 0 ? (const double *)nullptr : (const double *)s->d_wbuf64[(last - 1) % 2];
     rt::launch(apply_kernel, grid, BLOCK_THREADS, 0, s->stream, s->d_weights, s->d_w32, (const uint8_t *)s->d_w_fixed,
                s->d_gbuf[last % 3], ts, ts + W, W, s->plan_eta, s->opts.reg_param, (int)(s->opts.regularization == 1), w_in,
-               last ? s->d_gbuf[(last - 1) % 3] : (long long *)nullptr);
+               last ? s->d_gbuf[(last - 1) % 3] : (long long *)nullptr, (float *)nullptr);
   }
   weights_change(s);
   ++s->merged_sweeps;
@@ -1498,6 +1518,8 @@ int dwx_graph_get_info(const dwx_graph *g, dwx_graph_info *out) {
   out->num_query_variables = c.n_query;
   out->has_categorical = c.has_categorical; out->order_is_identity = c.order_is_identity;
   out->num_super_tiles = c.supers.size(); out->num_sorted_records = c.n_sorted;
+  out->max_super_tile_variables = 0;
+  for (const SuperTile &st : c.supers) out->max_super_tile_variables = std::max<uint64_t>(out->max_super_tile_variables, st.nv);
   out->grad_shift = c.grad_shift; out->grad_unit_max = c.grad_unit_max; out->max_records_per_weight = c.max_records_per_weight;
   return DWX_OK;
 }
@@ -1636,7 +1658,7 @@ int dwx_sampler_create(const dwx_graph *g, const dwx_options *opts, dwx_sampler 
       s->n_sort_dvals = (uint32_t)c.sort_dvals.size();
       s->sorted_learn = c.W > LDS_AGG_MAX_W;     // == their tiles are TILE_PULL
       // [UNI: one distinct d]; the RB builds are allowed by their first launch
-      const size_t lds_sorted = (size_t)SUPER_NV_MAX * 8 + SORT_TV_SLOTS * 4 + (size_t)s->n_sort_dvals * 8;
+      const size_t lds_sorted = sort_lds_bytes(s->n_sort_dvals);
       auto set = [&](SortedVariant &k, auto fn, bool rb) { k.fn = fn; k.lds = lds_sorted; if (!rb) k.allow(); };
       set(s->kv.sorted_infer[0][0], sorted_sweep_kernel<false, false>, false);
       set(s->kv.sorted_infer[0][1], sorted_sweep_kernel<false, false, true>, true);
@@ -2090,6 +2112,7 @@ int dwx_set_weights(dwx_sampler *s, const double *in) {
     rt::set_device(s->device);
     const uint32_t W = (uint32_t)s->cg->W;
     weights_change(s);
+    keep_snapshot(s);
     rt::h2d(s->d_weights, in, (size_t)W * 8, s->stream);
     if (W) {
       const unsigned grid = std::min<unsigned>((W + BLOCK_THREADS - 1) / BLOCK_THREADS, 2048u);
@@ -2112,6 +2135,7 @@ int dwx_average_weights_async(dwx_sampler *s, uint32_t n_replicas) {
       s->d_w_init = upload(s->cg->w_init, s->stream);
       rt::stream_sync(s->stream);
     }
+    keep_snapshot(s);
     const unsigned grid = std::min<unsigned>((W + BLOCK_THREADS - 1) / BLOCK_THREADS, 2048u);
     rt::launch(average_weights_kernel, grid, BLOCK_THREADS, 0, s->stream, s->d_weights, s->d_w32,
                (const uint8_t *)s->d_w_fixed, (const double *)s->d_w_init, W, (double)n_replicas);

@@ -70,6 +70,10 @@ float sorted_rec_d(const EdgeRec8 &c) {
 // with the second a fifth full; cut into 1024 equal ones they are half as dense: config 3's learning
 // sweep 0.36 -> 0.40 ms).  Otherwise (the layout of a split plan, one range per mini-batch chunk):
 // `slots` equal super-tiles per run, so that every chunk's launch is as wide as the chip.
+// The rest -- a whole run shorter than a full round: config 3's halves, 19 532 tiles on 256 slots of up to
+// 79 -- is shared out over the slots as equally as whole tiles allow (76 of 77 tiles and 180 of 76, not 253 of
+// 77 and a stub of 51), but not below 8 tiles a super-tile while the run has that many.
+// No super-tile holds more variables than super_nv_cap of the graph's table of distinct d (device_types.h).
 void build_sorted_layout(const CompiledGraph &g, const std::vector<std::pair<uint32_t, uint32_t>> &ranges,
                          uint32_t per_super, uint32_t slots, bool full_rounds, uint32_t nth, SortedLayout &out,
                          bool plan_only) {
@@ -77,11 +81,12 @@ void build_sorted_layout(const CompiledGraph &g, const std::vector<std::pair<uin
   if (g.edges8.size() == 0 || g.sort_dvals.empty()) return;
   per_super = std::max(1u, std::min(per_super, SORT_TV_SLOTS - 1));
   slots = std::max(1u, slots);
+  const uint32_t nv_cap = super_nv_cap((uint32_t)g.sort_dvals.size());
   auto emit = [&](uint32_t &i, uint32_t end, uint32_t per) {
     SuperTile st{};
     st.tile0 = i; st.v0 = g.tiles[i].v0;
     uint32_t nv = 0, j = i;
-    while (j < end && j - i < per && nv + g.tiles[j].nv <= SUPER_NV_MAX) nv += g.tiles[j++].nv;
+    while (j < end && j - i < per && nv + g.tiles[j].nv <= nv_cap) nv += g.tiles[j++].nv;
     st.ntiles = j - i; st.nv = nv;
     out.supers.push_back(st);
     i = j;
@@ -93,7 +98,11 @@ void build_sorted_layout(const CompiledGraph &g, const std::vector<std::pair<uin
         for (uint32_t k = 0; k < slots; ++k) emit(i, b, per_super);
     if (i == b) return;
     const uint32_t per = std::min(per_super, std::max((b - i + slots - 1) / slots, std::min(8u, per_super)));
-    while (i < b) emit(i, b, per);
+    // `left` super-tiles to go: as few as `per` allows, but every slot one where the slots are what decided `per`
+    // (a super-tile the variable cap cuts short leaves more tiles to the ones behind it)
+    uint32_t left = (b - i + per - 1) / per;
+    if ((b - i + slots - 1) / slots == per) left = std::max(left, std::min(slots, b - i));
+    for (; i < b; left = std::max(left, 2u) - 1) emit(i, b, std::min(per, (b - i + left - 1) / left));
   };
   for (const auto &rg : ranges) {
     uint32_t run0 = 0;
@@ -948,9 +957,6 @@ void compile_graph(const dwx_graph_desc &d, const dwx_compile_opts &o, CompiledG
     {
       uint64_t min_w = 4096;   // (a smaller table sits in the CU's L1: the plain stream gathers as fast)
       if (const char *e = getenv("DWX_SORTED_MIN_W")) min_w = (uint64_t)std::max(0L, atol(e));   // test hook
-      uint32_t want_super = o.super_tiles ? o.super_tiles : SUPER_TILES_DEFAULT;
-      if (const char *e = getenv("DWX_SUPER_TILES")) want_super = (uint32_t)std::max(1L, atol(e));   // experiment hook
-      const uint32_t per_super = std::min(want_super, SORT_TV_SLOTS - 1);   // (sorted_sweep_kernel's tile table)
       const uint32_t slots = o.sorted_slots ? o.sorted_slots : 256u * SORT_WG_PER_CU;
       if (g.edges8.size() && W >= min_w && !o.no_sorted_records) {
         // the distinct values of d = (sign(hit) - sign(miss)) * f over the eligible tiles' records
@@ -985,6 +991,10 @@ void compile_graph(const dwx_graph_desc &d, const dwx_compile_opts &o, CompiledG
           g.sort_dbits = dbits;
           g.sort_dvals.push_back(0.0);
           for (uint32_t b : dbits) { float f; std::memcpy(&f, &b, 4); g.sort_dvals.push_back((double)f); }
+          // (the default: as many full tiles as the LDS holds sums for beside this table of d)
+          uint32_t want_super = o.super_tiles ? o.super_tiles : super_tiles_default((uint32_t)g.sort_dvals.size());
+          if (const char *e = getenv("DWX_SUPER_TILES")) want_super = (uint32_t)std::max(1L, atol(e));   // experiment hook
+          const uint32_t per_super = std::min(want_super, SORT_TV_SLOTS - 1);   // (sorted_sweep_kernel's tile table)
           g.sorted_per_super = per_super; g.sorted_slots = slots;
           // the default layout: every launch's query tiles and evidence tiles on their own (an
           // inference sweep launches over the query part only), full rounds first

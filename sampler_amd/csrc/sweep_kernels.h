@@ -734,7 +734,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS, TAB ? 4 : (LEARN ? DWX_S8_LEARN
 // What bounded sweep8_kernel on a graph with a million weights was one L2 request per record:
 // the weight gathers of a variable-major record stream are random.  Here ONE WORKGROUP of
 // SORT_THREADS = 1024 lanes -- the CU's whole LDS, one workgroup per CU -- takes a super-tile: up to
-// SUPER_NV_MAX = 16 384 consecutive boolean variables of an all-unary graph (<= 64 tiles), and
+// super_nv_cap(n_dvals) = 19 200 to 20 224 consecutive boolean variables of an all-unary graph (75 to 79 tiles), and
 // streams the super-tile's records in the order of their WEIGHT IDS (the second, sorted copy of
 // graph_compile.cc; SORT_K = 20 coalesced 8-byte loads in flight per lane, the next step's records
 // under this step's gathers): the 64 lanes of a wave-instruction gather ascending, neighbouring
@@ -748,7 +748,8 @@ __global__ void __launch_bounds__(BLOCK_THREADS, TAB ? 4 : (LEARN ? DWX_S8_LEARN
 // the per-variable words of the next pass in flight under the current one: the tiles' own
 // process_variable (W_FIXSUM: the potential is given) draws, stores, tallies, and -- learning --
 // publishes the wave ballots of the pull gradient exactly where sweep8_kernel puts them.
-// LDS: 128 KiB of sums + the tile starts + the table of distinct d values (<= 1024; none when UNI).
+// LDS (160 KiB, sort_lds_bytes): the tile starts, the table of distinct d values (<= 1024; not read when UNI), then the
+// sums -- as many as the rest holds, which is what caps a super-tile (device_types.h: super_nv_cap).
 // Replaces, for these variables, FactorGraph::potential's loop (src/factor_graph.h:127-145) and
 // draw_sample (src/gibbs_sampler.h:198-215).
 
@@ -760,9 +761,10 @@ __global__ void __launch_bounds__(SORT_THREADS, SORT_WG_PER_CU)
 sorted_sweep_kernel(const KernelParams P, const SuperTile *supers, uint32_t n_supers, const SortRec8 *recs,
                     const double *dvals, uint32_t n_dvals) {
   DWX_DYN_LDS(dyn_lds);
-  unsigned long long *s_acc = (unsigned long long *)dyn_lds;            // [SUPER_NV_MAX]
-  uint32_t *s_tv = (uint32_t *)(dyn_lds + SUPER_NV_MAX * sizeof(long long));   // [SORT_TV_SLOTS] first variable of every tile (+ end)
-  double *s_d = (double *)(dyn_lds + SUPER_NV_MAX * sizeof(long long) + SORT_TV_SLOTS * sizeof(uint32_t));   // [n_dvals]
+  uint32_t *s_tv = (uint32_t *)dyn_lds;                                 // [SORT_TV_SLOTS] first variable of every tile (+ end)
+  double *s_d = (double *)(dyn_lds + sort_acc_offset(0));               // [n_dvals]
+  // [super_nv_cap(n_dvals)] (UNI: at a constant offset -- the table is not read, the sums may lie over it)
+  unsigned long long *s_acc = (unsigned long long *)(dyn_lds + sort_acc_offset(UNI ? 0u : DWX_UNIFORM(n_dvals)));
   const uint32_t t = threadIdx.x;
   if (blockIdx.x >= n_supers) return;
   // (P.super_rot: the launch starts at that super-tile and wraps round -- launch_tiles)

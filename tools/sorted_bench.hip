@@ -8,9 +8,10 @@
 //
 // Not product code: a calibration tool (run by hand; results in profiles/r03/sorted_bench.jsonl).
 //
-//   sorted_bench [--records N] [--weights W] [--ceiling]
+//   sorted_bench [--records N] [--weights W] [--ceiling | --rounds]
 // one JSON line per (NV, threads, workgroups per CU, sorted?, atomics?); --ceiling: only the
-// product kernel's shape, on one full round of 256 super-tiles (bench.py: roofline.secondary)
+// product kernel's shape, on one full round of 256 super-tiles (bench.py: roofline.secondary); --rounds: one
+// config-3 half cut into two rounds of super-tiles against one round of larger ones (profiles/r14)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -135,6 +136,132 @@ __global__ void __launch_bounds__(THREADS) sorted6_kernel(const uint32_t *__rest
   }
 }
 
+// --rounds (round 14): the product's launch shape instead of a persistent loop -- ONE workgroup of 1024 lanes per
+// super-tile, in the order of the list, super-tiles of different sizes, the owner in OB bits below the index of d
+// (1 here; 0 = a zero-filled lane past the end, as in sorted_sweep_kernel).  KK records in flight per lane.
+struct Super { uint64_t rec0; uint32_t v0, nv; };
+template <int KK, int OB>
+__global__ void __launch_bounds__(1024) rounds_kernel(const u32x2 *__restrict__ recs, const float *__restrict__ w32,
+                                                      const Super *__restrict__ supers, uint32_t n_super,
+                                                      uint32_t *__restrict__ out) {
+  extern __shared__ unsigned long long acc[];
+  constexpr uint32_t THREADS = 1024, MASK = (1u << OB) - 1;
+  const uint32_t t = threadIdx.x;
+  if (blockIdx.x >= n_super) return;
+  const Super S = supers[blockIdx.x];
+  const uint32_t nv = __builtin_amdgcn_readfirstlane(S.nv), per = nv * PER_VAR;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(recs + S.rec0), 0, (int)(per * 8u), 0x00020000);
+  u32x2 rec[KK];
+#pragma unroll
+  for (int k = 0; k < KK; ++k) rec[k] = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(t * 8u), (int)(k * THREADS * 8), 2);
+  for (uint32_t i = t; i < nv; i += THREADS) acc[i] = 0;
+  __syncthreads();
+  for (uint32_t first = 0; first < per; first += KK * THREADS) {
+    float w[KK];
+#pragma unroll
+    for (int k = 0; k < KK; ++k) w[k] = w32[rec[k].x];
+    u32x2 cur[KK];
+#pragma unroll
+    for (int k = 0; k < KK; ++k) cur[k] = rec[k];
+    const uint32_t nxt = (first + KK * THREADS) * 8u;
+#pragma unroll
+    for (int k = 0; k < KK; ++k) rec[k] = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(t * 8u), (int)(nxt + k * THREADS * 8), 2);
+#pragma unroll
+    for (int k = 0; k < KK; ++k) {
+      const long long q = fix32((double)w[k] * 2.0);
+      const uint32_t owner = cur[k].y & MASK;
+      if (cur[k].y >> OB) atomicAdd(&acc[owner < nv ? owner : 0], (unsigned long long)q);
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = t; i < nv; i += THREADS) {
+    const double x = (double)(long long)acc[i] * (1.0 / 4294967296.0);
+    const float q = 0.37f * (1.0f + __expf((float)-x));
+    out[(size_t)S.v0 + i] = q < 1.0f ? 1u : 0u;
+  }
+}
+
+// One half of config 3 (19 543 tiles of 256 variables, ten records each, 1 M weights) cut the way the product cuts
+// it: `two_round` = 256 super-tiles of 64 tiles and 243 of 13 (14-bit owners, 128 KiB of sums), `one_round` = 256 of
+// 76 or 77 tiles (15-bit owners, up to 154 KiB of sums).  One JSON line per shape and run, the shapes alternating.
+struct Shape {
+  const char *name; int k, owner_bits;
+  std::vector<uint32_t> nvs;
+  u32x2 *recs = nullptr; Super *supers = nullptr; size_t lds = 0;
+};
+static void build_shape(Shape &sh, uint32_t W) {
+  std::vector<Super> sup;
+  uint64_t at = 0; uint32_t v = 0, nv_max = 0;
+  for (uint32_t nv : sh.nvs) { sup.push_back(Super{at, v, nv}); at += (uint64_t)nv * PER_VAR; v += nv; nv_max = std::max(nv_max, nv); }
+  std::vector<u32x2> h(at);
+  // 16 distinct super-tiles of every size, repeated: random weight ids, sorted; every variable PER_VAR records
+  std::vector<std::thread> th;
+  const uint32_t flag = 1u << sh.owner_bits;
+  for (uint32_t s = 0; s < 16; ++s)
+    th.emplace_back([&, s]() {
+      std::vector<size_t> first_of;   // the first super-tile of each size this thread has met
+      std::vector<uint32_t> met;
+      for (size_t i = s; i < sup.size(); i += 16) {
+        const uint32_t per = sup[i].nv * PER_VAR;
+        u32x2 *r = h.data() + sup[i].rec0;
+        size_t j = 0;
+        while (j < met.size() && met[j] != sup[i].nv) ++j;
+        if (j < met.size()) { memcpy(r, h.data() + sup[first_of[j]].rec0, (size_t)per * 8); continue; }
+        met.push_back(sup[i].nv); first_of.push_back(i);
+        std::mt19937 rng(1234 + s + 16 * (uint32_t)j);
+        for (uint32_t e = 0; e < per; ++e) { r[e].x = rng() % W; r[e].y = (e / PER_VAR) | flag; }
+        std::shuffle(r, r + per, rng);
+        std::sort(r, r + per, [](const u32x2 &a, const u32x2 &b) { return a.x < b.x; });
+      }
+    });
+  for (auto &t : th) t.join();
+  CK(hipMalloc(&sh.recs, at * 8 + (1u << 20)));
+  CK(hipMemcpy(sh.recs, h.data(), at * 8, hipMemcpyHostToDevice));
+  CK(hipMalloc(&sh.supers, sup.size() * sizeof(Super)));
+  CK(hipMemcpy(sh.supers, sup.data(), sup.size() * sizeof(Super), hipMemcpyHostToDevice));
+  sh.lds = (size_t)nv_max * 8 + 512;   // (+ the product's table of tile starts)
+}
+static int run_rounds(uint32_t W, const float *w32) {
+  std::vector<uint32_t> two(256, 16384u), one;
+  two.insert(two.end(), 243, 3328u);
+  const uint32_t tiles = 256 * 64 + 243 * 13;           // 19 543
+  for (uint32_t i = 0; i < 256; ++i) one.push_back(256u * (tiles / 256 + (i < tiles % 256 ? 1u : 0u)));
+  Shape shapes[4] = {{"two_round", 20, 14, two}, {"one_round", 20, 15, one}, {"one_round", 16, 15, one}, {"one_round", 24, 15, one}};
+  uint32_t *out = nullptr;
+  CK(hipMalloc(&out, (size_t)tiles * 256 * 4));
+  for (int i = 0; i < 2; ++i) build_shape(shapes[i], W);
+  for (int i = 2; i < 4; ++i) { shapes[i].recs = shapes[1].recs; shapes[i].supers = shapes[1].supers; shapes[i].lds = shapes[1].lds; }
+  hipEvent_t a, b;
+  CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
+  for (int run = 0; run < 6; ++run)
+    for (Shape &sh : shapes) {
+      auto go = [&](auto kern) {
+        CK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.lds));
+        float ms[4];
+        for (int rep = 0; rep < 4; ++rep) {    // (the first one warms up: not reported)
+          CK(hipEventRecord(a, 0));
+          hipLaunchKernelGGL(kern, dim3((unsigned)sh.nvs.size()), dim3(1024), sh.lds, 0, (const u32x2 *)sh.recs, w32,
+                             (const Super *)sh.supers, (uint32_t)sh.nvs.size(), out);
+          CK(hipEventRecord(b, 0));
+          CK(hipEventSynchronize(b));
+          CK(hipEventElapsedTime(&ms[rep], a, b));
+        }
+        CK(hipGetLastError());
+        std::sort(ms + 1, ms + 4);
+        const double n = (double)tiles * 256 * PER_VAR;
+        printf("{\"shape\": \"%s\", \"k\": %d, \"owner_bits\": %d, \"super_tiles\": %zu, \"lds_bytes\": %zu, \"run\": %d, "
+               "\"records\": %.0f, \"ms\": %.4f, \"ms_min\": %.4f, \"ms_max\": %.4f, \"records_per_s\": %.4g}\n",
+               sh.name, sh.k, sh.owner_bits, sh.nvs.size(), sh.lds, run, n, ms[2], ms[1], ms[3], n / (ms[2] * 1e-3));
+        fflush(stdout);
+      };
+      if (sh.owner_bits == 14) go(rounds_kernel<20, 14>);
+      else if (sh.k == 16) go(rounds_kernel<16, 15>);
+      else if (sh.k == 24) go(rounds_kernel<24, 15>);
+      else go(rounds_kernel<20, 15>);
+    }
+  return 0;
+}
+
 struct Cfg { uint32_t nv; int threads, wg_per_cu; bool sorted, atomics; };
 
 int main(int argc, char **argv) {
@@ -142,8 +269,10 @@ int main(int argc, char **argv) {
   uint32_t W = 1u << 20;
   bool ceiling_only = false;    // one line: the product kernel's shape (16 384 variables, 1024 threads, 1 per CU)
   bool rec6 = false;            // the product's shape over 8-byte and over 6-byte records, side by side
+  bool rounds = false;          // one config-3 half as two rounds of super-tiles and as one (run_rounds)
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--rec6")) rec6 = true;
+    if (!strcmp(argv[i], "--rounds")) rounds = true;
     if (!strcmp(argv[i], "--ceiling")) { ceiling_only = true; nrec = 42ull * 1000 * 1000; }
     if (i + 1 < argc && !strcmp(argv[i], "--records")) nrec = strtoull(argv[i + 1], nullptr, 10);
     if (i + 1 < argc && !strcmp(argv[i], "--weights")) W = (uint32_t)strtoul(argv[i + 1], nullptr, 10);
@@ -158,6 +287,7 @@ int main(int argc, char **argv) {
     CK(hipMalloc(&w32, (size_t)W * 4));
     CK(hipMemcpy(w32, hw.data(), (size_t)W * 4, hipMemcpyHostToDevice));
   }
+  if (rounds) return run_rounds(W, w32);
   u32x2 *recs = nullptr;
   uint32_t *out = nullptr;
   CK(hipMalloc(&recs, nrec * 8 + (1u << 20)));

@@ -200,6 +200,68 @@ pull_ell_kernel(const U32x4 *__restrict__ ell, const uint32_t *block_tile0, uint
   }
 }
 
+// One-plane packed rows (device_types.h: bp1_pack_entry; the builders' form of a one-delta table whose owners
+// are all boolean evidence variables): an entry's sign is in its row, so only the nz words of the block's ballot
+// pairs go to LDS -- as 8-byte words, pair i of the block at s_nz[i]; the pairs lie 16 bytes apart in `delta` --
+// and a slot costs one 32-bit LDS read.  A block holds up to BP1_TILES tiles (`tiles`: the table's block size;
+// the allocation of `delta` is padded by one full block).  The byte partials are those of
+// pull_ell_kernel<DEPTH, true, true>: fold_partials_kernel<true> consumes them alike.
+template <int DEPTH>
+__global__ void __launch_bounds__(BP_THREADS)
+pull_ell1_kernel(const unsigned long long *__restrict__ ell, const uint32_t *block_tile0, uint32_t parts, uint32_t tiles,
+                 uint32_t Wp, const unsigned long long *delta, signed char *__restrict__ partial) {
+  DWX_DYN_LDS(dyn_lds);
+  unsigned long long *s_nz = (unsigned long long *)dyn_lds;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t b = blockIdx.x / parts, part = blockIdx.x % parts;
+  const DeltaPair *src = (const DeltaPair *)delta + (size_t)block_tile0[b] * 4;   // (padded allocation)
+  const uint32_t pairs = umin(tiles, BP1_TILES) * 4u;
+  for (uint32_t i = tid; i < pairs; i += BP_THREADS) s_nz[i] = src[i].nz;
+  const uint32_t *s_words = (const uint32_t *)s_nz;
+  __syncthreads();
+  // A lane owns TWO consecutive weights: one 16-byte load per plane takes both words (the planes are [Wp], Wp a
+  // multiple of BP_THREADS: 16-byte aligned at an even weight), and their two byte counts leave as one 16-bit
+  // store.  This part's weights: whole groups of 2 * BP_THREADS; the last group of the table may be half a one.
+  static_assert(BP_UNROLL % 2 == 0, "two weights per lane");
+  constexpr uint32_t U2 = BP_UNROLL / 2, GROUP = 2 * BP_THREADS;
+  const uint32_t groups = (Wp + GROUP - 1) / GROUP, per = (groups + parts - 1) / parts;
+  const uint32_t g0 = part * per, g1 = g0 + per < groups ? g0 + per : groups;
+  const unsigned long long *__restrict__ rows8 = ell + (size_t)b * DEPTH * Wp;
+  signed char *__restrict__ out8 = partial + (size_t)b * Wp;
+  for (uint32_t g = g0; g < g1; g += U2) {
+    U32x4 row[U2][DEPTH];
+#pragma unroll
+    for (uint32_t u = 0; u < U2; ++u) {
+      const uint32_t w = umin(umin(g + u, g1 - 1) * GROUP + 2u * tid, Wp - 2u);   // (past the end: loaded again, not stored)
+#pragma unroll
+      for (int dd = 0; dd < DEPTH; ++dd) row[u][dd] = DWX_LOAD_ROW_NT((const U32x4 *)&rows8[(size_t)dd * Wp + w]);
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < U2; ++u) {
+      int cnt[2] = {0, 0};   // (at most BP_PK_ROW * DEPTH entries each: a byte)
+#pragma unroll
+      for (int dd = 0; dd < DEPTH; ++dd) {
+#pragma unroll
+        for (uint32_t h = 0; h < 2; ++h) {
+          const uint32_t lo = row[u][dd].v[2 * h], hi = row[u][dd].v[2 * h + 1];
+          const unsigned long long e = ((unsigned long long)hi << 32) | lo;
+          const uint32_t n = (hi >> (BP1_COUNT_SHIFT - 32)) & 3u, npos = hi >> (BP1_NPOS_SHIFT - 32);
+#pragma unroll
+          for (uint32_t k = 0; k < BP_PK_ROW; ++k) {
+            // branch-free: an unused slot reads the bit of slot 0 and adds zero
+            const uint32_t slot = (uint32_t)(e >> (BP1_SLOT_BITS * k)) & BP1_SLOT_MASK;
+            const int bit = (int)((s_words[slot >> 5] >> (slot & 31u)) & 1u);
+            cnt[h] += k < n ? (k < npos ? bit : -bit) : 0;
+          }
+        }
+      }
+      const uint32_t w = (g + u) * GROUP + 2u * tid;
+      if (g + u < g1 && w < Wp)
+        DWX_NT_STORE((unsigned short)(((uint32_t)cnt[0] & 255u) | (((uint32_t)cnt[1] & 255u) << 8)), (unsigned short *)&out8[w]);
+    }
+  }
+}
+
 // grad[w] += sum over blocks of partial[block][w]  (UNIFORM: byte counts of the one step q0), plus the
 // entries that did not fit the blocks' rows: they stay on the weight-sorted list, weight w's at
 // [ov_start[w], ov_start[w + 1]) of inc_slot / inc_d (ov_start == nullptr: none), and the lane that owns

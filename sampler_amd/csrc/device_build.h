@@ -47,8 +47,11 @@ void build_static_tables(const TileDesc *d_tiles, uint32_t n_tiles, const uint32
 // few distinct deltas -- per group the block-pull table (rows of BP_ROW x depth entries per (variable
 // block, weight)), with what did not fit a row left on the list and the per-weight starts of those leftovers.  Bit for bit the host builder's
 // structures.  h_tile_info[tile] = group | mode << 30 (1: all records, 2: pre-signed ones only),
-// 0xFFFFFFFF: none.  The device buffers of the result belong to the caller (hipFree / rt::dfree).
+// 0xFFFFFFFF: none.  bp_tiles: tiles per block, 0 = the row format's default.  `out` also brings two inputs, set by the
+// caller before the call: groups that qualify (bp_one_plane) take the one-plane rows when out.d_v_init is not null --
+// their signs come from it.  The device buffers of the result belong to the caller (hipFree / rt::dfree).
 struct Incidence {
+  const uint32_t *d_v_init = nullptr;            // IN: [V] dense evidence values, or null: no one-plane rows (DWX_BP_TWO_PLANES=1)
   uint64_t n_entries = 0;
   std::vector<uint32_t> inc_begin, inc_end;      // per group: its part of the list columns (multiples of PULL_RUN)
   uint32_t *d_inc_wid = nullptr, *d_inc_slot = nullptr;
@@ -58,6 +61,8 @@ struct Incidence {
     uint32_t *d_ov_start = nullptr;              // [W + 1]: where each weight's leftovers start in the group's list
     std::vector<uint32_t> tile0;
     uint32_t blocks = 0, depth = 0;              // depth: 16-byte rows of 4 entries, or (one delta) 8-byte planes of 3
+    uint32_t tiles = 0;                          // tiles per block (bp_block_tiles)
+    bool one_plane = false;                      // the rows are one-plane packed words (device_types.h: bp1_pack_entry)
     uint64_t total = 0, on_list = 0;             // the group's entries; those left on the list
   };
   std::vector<BlockTable> bp;                    // [groups], or empty: no block pull

@@ -268,7 +268,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS)
 incidence_emit_kernel(const TileDesc *tiles, uint32_t n_tiles, const uint32_t *tile_info, const uint32_t *v_meta,
                       const uint32_t *v_row, const uint32_t *row_ptr, const EdgeRec *edges, uint32_t learn_non_evidence,
                       uint32_t noise_aware, unsigned long long *tile_count, const unsigned long long *tile_base,
-                      unsigned long long *keys, unsigned long long *vals) {
+                      unsigned long long *keys, unsigned long long *vals, uint32_t *other_owner) {
   __shared__ uint32_t s_n[BLOCK_THREADS];
   const uint32_t ti = blockIdx.x, l = threadIdx.x;
   if (ti >= n_tiles) return;
@@ -278,8 +278,10 @@ incidence_emit_kernel(const TileDesc *tiles, uint32_t n_tiles, const uint32_t *t
   const bool unary_only = (info >> 30) == 2u;
   const TileDesc td = tiles[ti];
   uint32_t e0 = 0, e1 = 0;
+  bool other = false;      // (not a boolean evidence variable: its group's rows keep both ballot planes)
   if (l < td.nv) {
     const uint32_t p = td.v0 + l, m = v_meta[p];
+    other = (m & VM_CATEGORICAL) || !(m & VM_EVIDENCE);
     if (learn_non_evidence || (!noise_aware && (m & VM_EVIDENCE))) { e0 = row_ptr[v_row[p]]; e1 = row_ptr[v_row[p] + 1]; }
   }
   auto wanted = [&](const EdgeRec r, float &dd) {
@@ -292,6 +294,7 @@ incidence_emit_kernel(const TileDesc *tiles, uint32_t n_tiles, const uint32_t *t
   };
   uint32_t n = 0;
   for (uint32_t e = e0; e < e1; ++e) { float dd; n += wanted(edges[e], dd) ? 1u : 0u; }
+  if (COUNT && n && other && !other_owner[group]) other_owner[group] = 1u;
   s_n[l] = n;
   __syncthreads();
   for (uint32_t off = 1; off < BLOCK_THREADS; off <<= 1) {      // inclusive scan
@@ -366,7 +369,7 @@ __global__ void __launch_bounds__(256)
 ell_walk_kernel(const unsigned long long *vals, uint64_t g0, const uint32_t *w_at, uint32_t W, const uint32_t *block_of,
                 const uint32_t *tile0, uint32_t depth, uint64_t Wp, const uint32_t *dvals, uint32_t n_dvals, U32x4 *ell,
                 uint32_t packed, uint32_t *ov, const uint32_t *ovs, const unsigned long long *keys, unsigned long long *kept_keys,
-                unsigned long long *kept_vals, uint64_t kept_base) {
+                unsigned long long *kept_vals, uint64_t kept_base, const TileDesc *tiles, const uint32_t *v_init) {
   const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= W) return;
   const uint32_t cap = (packed ? BP_PK_ROW : BP_ROW) * depth;
@@ -375,9 +378,32 @@ ell_walk_kernel(const unsigned long long *vals, uint64_t g0, const uint32_t *w_a
   for (uint64_t i = g0 + w_at[w]; i < g0 + w_at[w + 1]; ++i) {
     const unsigned long long v = vals[i];
     const uint32_t slot = (uint32_t)(v >> 32), ti = slot / BLOCK_THREADS, vb = block_of[ti];
-    if (vb != cur) { cur = vb; kk = 0; }
+    if (vb != cur) {
+      cur = vb; kk = 0;
+      if (FILL && v_init) {
+        // one-plane rows: the block's first `cap` entries, those that step by +q (v_init != 1) first
+        const uint64_t end = g0 + w_at[w + 1];
+        uint64_t e1 = i;
+        uint32_t n_plus = 0;
+        auto plus = [&](uint32_t s) { return v_init[tiles[s / BLOCK_THREADS].v0 + s % BLOCK_THREADS] != 1u; };
+        while (e1 < end && e1 - i < cap && block_of[(uint32_t)(vals[e1] >> 32) / BLOCK_THREADS] == vb) {
+          n_plus += plus((uint32_t)(vals[e1] >> 32)) ? 1u : 0u;
+          ++e1;
+        }
+        uint32_t at_plus = 0, at_minus = n_plus;
+        for (uint64_t j = i; j < e1; ++j) {
+          const uint32_t s = (uint32_t)(vals[j] >> 32);
+          const bool p = plus(s);
+          const uint32_t at = p ? at_plus++ : at_minus++;
+          unsigned long long *word = (unsigned long long *)ell + ((uint64_t)vb * depth + at / BP_PK_ROW) * Wp + w;
+          *word = bp1_pack_entry(*word, at % BP_PK_ROW, (s / BLOCK_THREADS - tile0[vb]) * BLOCK_THREADS + s % BLOCK_THREADS, p);
+        }
+      }
+    }
     if (kk < cap) {
-      if (FILL && packed) {      // (the lane owns its weight's words: plain read-modify-write; the host zeroed them)
+      if (FILL && v_init) {
+        // (written with the block's first entry)
+      } else if (FILL && packed) {      // (the lane owns its weight's words: plain read-modify-write; the host zeroed them)
         unsigned long long *word = (unsigned long long *)ell + ((uint64_t)vb * depth + kk / BP_PK_ROW) * Wp + w;
         *word = bp_pack_entry(*word, kk % BP_PK_ROW, (ti - tile0[vb]) * BLOCK_THREADS + slot % BLOCK_THREADS);
       } else if (FILL) {
@@ -572,6 +598,8 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
                      const uint32_t *d_v_meta, const uint32_t *d_v_row, const uint32_t *d_row_ptr, const EdgeRec *d_edges,
                      bool learn_non_evidence, bool noise_aware, uint32_t W, uint32_t n_groups, uint64_t block_pull_min_w,
                      uint32_t bp_tiles, Incidence &out, void *stream_v) {
+  const uint32_t *d_v_init = out.d_v_init;      // (input: null = no one-plane rows)
+  const bool allow_one_plane = d_v_init != nullptr;
   hipStream_t st = (hipStream_t)stream_v;
   out = Incidence();
   out.inc_begin.assign(n_groups, 0); out.inc_end.assign(n_groups, 0);
@@ -594,13 +622,17 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
     // ---- entries: count per tile, scan on the host (a few hundred thousand tiles), emit, sort ----
     uint32_t *d_info = (uint32_t *)dalloc((size_t)n_tiles * 4);
     unsigned long long *d_cnt = (unsigned long long *)dalloc((size_t)n_tiles * 8);
+    uint32_t *d_other = (uint32_t *)dalloc((size_t)n_groups * 4);      // per group: an owner that is no boolean evidence variable
     DEVB_HIP(hipMemcpyAsync(d_info, h_tile_info, (size_t)n_tiles * 4, hipMemcpyHostToDevice, st));
+    DEVB_HIP(hipMemsetAsync(d_other, 0, (size_t)n_groups * 4, st));
     hipLaunchKernelGGL(incidence_emit_kernel<true>, dim3(n_tiles), dim3(BLOCK_THREADS), 0, st, d_tiles, n_tiles,
                        (const uint32_t *)d_info, d_v_meta, d_v_row, d_row_ptr, d_edges, (uint32_t)learn_non_evidence,
                        (uint32_t)noise_aware, d_cnt, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                       (unsigned long long *)nullptr);
+                       (unsigned long long *)nullptr, d_other);
     DEVB_HIP(hipGetLastError());
     std::vector<unsigned long long> base(n_tiles + 1, 0);
+    std::vector<uint32_t> other_owner(n_groups, 0);
+    DEVB_HIP(hipMemcpyAsync(other_owner.data(), d_other, (size_t)n_groups * 4, hipMemcpyDeviceToHost, st));
     DEVB_HIP(hipMemcpyAsync(base.data() + 1, d_cnt, (size_t)n_tiles * 8, hipMemcpyDeviceToHost, st));
     DEVB_HIP(hipStreamSynchronize(st));
     for (uint32_t t = 0; t < n_tiles; ++t) base[t + 1] += base[t];
@@ -615,7 +647,8 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
     step("allocate 4 x n x 8 bytes");
     hipLaunchKernelGGL(incidence_emit_kernel<false>, dim3(n_tiles), dim3(BLOCK_THREADS), 0, st, d_tiles, n_tiles,
                        (const uint32_t *)d_info, d_v_meta, d_v_row, d_row_ptr, d_edges, (uint32_t)learn_non_evidence,
-                       (uint32_t)noise_aware, (unsigned long long *)nullptr, (const unsigned long long *)d_cnt, k0, v0);
+                       (uint32_t)noise_aware, (unsigned long long *)nullptr, (const unsigned long long *)d_cnt, k0, v0,
+                       (uint32_t *)nullptr);
     DEVB_HIP(hipGetLastError());
     step("emit");
     uint32_t gbits = 0;
@@ -666,16 +699,19 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
     if (enabled) {
       std::vector<uint32_t> block_of(n_tiles, 0), tile0_all;
       std::vector<uint64_t> tile0_off(n_groups + 1, 0);
-      std::vector<uint32_t> depth(n_groups, 0);
+      std::vector<uint32_t> depth(n_groups, 0), tiles_of(n_groups, 0);
+      std::vector<uint8_t> one_plane(n_groups, 0);
       const bool packed = dvals.size() == 1;      // one delta: three 19-bit slots per 8-byte word, zero = no entry
       const size_t row_bytes = packed ? 8 : sizeof(U32x4);
       for (uint32_t k = 0; k < n_groups; ++k) {
         tile0_off[k] = tile0_all.size();
         if (!kept_n[k]) continue;
         const size_t first = tile0_all.size();
+        one_plane[k] = bp_one_plane(dvals.size(), learn_non_evidence, noise_aware, !other_owner[k], allow_one_plane);
+        tiles_of[k] = (uint32_t)bp_block_tiles(one_plane[k], bp_tiles);
         for (uint32_t ti = 0; ti < n_tiles; ++ti) {
           if (!has[ti] || (h_tile_info[ti] & 0x3FFFFFFFu) != k || h_tile_info[ti] == 0xFFFFFFFFu) continue;
-          if (tile0_all.size() == first || ti >= tile0_all.back() + bp_tiles) tile0_all.push_back(ti);
+          if (tile0_all.size() == first || ti >= tile0_all.back() + tiles_of[k]) tile0_all.push_back(ti);
           block_of[ti] = (uint32_t)(tile0_all.size() - first) - 1;
         }
         const uint64_t nvb = tile0_all.size() - first;
@@ -706,7 +742,8 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
         hipLaunchKernelGGL(ell_walk_kernel<true>, dim3(wgrid), dim3(256), 0, st, vals, g0, (const uint32_t *)d_wat, W,
                            (const uint32_t *)d_block_of, (const uint32_t *)(d_tile0 + tile0_off[k]), depth[k], Wp,
                            (const uint32_t *)d_dvals, (uint32_t)dvals.size(), ell_now, (uint32_t)packed, d_ov, (const uint32_t *)nullptr, keys,
-                           (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint64_t)0);
+                           (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint64_t)0, d_tiles,
+                           one_plane[k] ? d_v_init : (const uint32_t *)nullptr);
         DEVB_HIP(hipGetLastError());
         DEVB_HIP(rocprim::exclusive_scan(scan_tmp, scan_bytes, d_ov, d_ovs, 0u, (size_t)W, rocprim::plus<uint32_t>(), st));
         uint32_t last_ov = 0, last_ovs = 0;
@@ -723,13 +760,14 @@ void build_incidence(const TileDesc *d_tiles, const TileDesc *h_tiles, uint32_t 
           hipLaunchKernelGGL(ell_walk_kernel<false>, dim3(wgrid), dim3(256), 0, st, vals, g0, (const uint32_t *)d_wat, W,
                              (const uint32_t *)d_block_of, (const uint32_t *)(d_tile0 + tile0_off[k]), depth[k], Wp,
                              (const uint32_t *)d_dvals, (uint32_t)dvals.size(), (U32x4 *)nullptr, (uint32_t)packed, (uint32_t *)nullptr,
-                             (const uint32_t *)d_ovs, keys, kk, kv, g0);
+                             (const uint32_t *)d_ovs, keys, kk, kv, g0, d_tiles, (const uint32_t *)nullptr);
         DEVB_HIP(hipGetLastError());
         Incidence::BlockTable &bt = out.bp[k];
         bt.d_ell = ell_now; ell_now = nullptr;
         bt.d_ov_start = ovs_now; ovs_now = nullptr;
         bt.tile0.assign(tile0_all.begin() + tile0_off[k], tile0_all.begin() + tile0_off[k + 1]);
         bt.blocks = (uint32_t)nvb; bt.depth = depth[k];
+        bt.tiles = tiles_of[k]; bt.one_plane = one_plane[k] != 0;
         bt.total = g1 - g0; bt.on_list = kept_n[k];
         max_blocks = std::max(max_blocks, nvb);
       }

@@ -259,6 +259,38 @@ constexpr uint32_t bp_row_depth(double lambda, bool packed) {
 constexpr uint32_t FOLD_W = 4;                    // consecutive weights per lane of fold_partials_kernel
 // one block of ballot pairs + the table of deltas: exactly the 160 KiB of a CU
 constexpr uint32_t BP_LDS_BYTES = BP_TILES * 64 + BP_DELTA_SLOTS * 8;
+// One-plane packed rows (pull_ell1_kernel).  Where every owner of a one-delta table is a boolean evidence
+// variable of a sampler with learn_non_evidence and noise_aware off, the evidence chain holds v_init, so the
+// second ballot plane is static: ng == nz & (v_init == 1), and an entry's sign is known when the table is built.
+// Only the nz words of a block go to LDS -- 32 bytes per tile, BP1_TILES tiles in 128 KiB -- and a word holds
+// BP_PK_ROW 20-bit slots, slot k in bits 20 k .. 20 k + 19, in bits 60-61 how many of them hold an entry (filled
+// from slot 0) and in bits 62-63 how many of those, counted from slot 0, step by +q; the others step by -q (their
+// owner's v_init is 1).  Over the planes of one (block, weight) row the +q entries come first, each kind in list
+// order.  As in the two-plane packed rows no slot code is reserved: 0xFFFFF is the last lane of a full block.
+constexpr uint32_t BP1_TILES = 4096, BP1_SLOT_BITS = 20, BP1_SLOT_MASK = (1u << BP1_SLOT_BITS) - 1;
+constexpr uint32_t BP1_COUNT_SHIFT = 60, BP1_NPOS_SHIFT = 62;
+constexpr uint32_t BP1_LDS_BYTES = BP1_TILES * 32;
+#ifndef DWX_BP1_TILES_DEFAULT
+#define DWX_BP1_TILES_DEFAULT 3328
+#endif
+constexpr uint32_t BP1_TILES_DEFAULT = DWX_BP1_TILES_DEFAULT;   // (profiles/r15: the block size with the smallest pull + fold)
+static_assert(BP1_TILES_DEFAULT >= 1 && BP1_TILES_DEFAULT <= BP1_TILES, "a block's nz words must fit BP1_LDS_BYTES");
+// the entry at position k of its word (any order of calls, as long as the +q entries end up in the lowest positions)
+constexpr unsigned long long bp1_pack_entry(unsigned long long word, uint32_t k, uint32_t code, bool plus) {
+  const unsigned long long n = (word >> BP1_COUNT_SHIFT) & 3u, npos = (word >> BP1_NPOS_SHIFT) + (plus ? 1u : 0u);
+  return (word & ((1ull << BP1_COUNT_SHIFT) - 1)) | ((unsigned long long)code << (BP1_SLOT_BITS * k)) |
+         ((n > k + 1u ? n : k + 1u) << BP1_COUNT_SHIFT) | (npos << BP1_NPOS_SHIFT);
+}
+// Which groups take the one-plane rows (both builders): `owners_ok` = every owner of the group's entries is a
+// boolean VM_EVIDENCE variable; `allowed` = not switched off (DWX_BP_TWO_PLANES=1).
+constexpr bool bp_one_plane(uint64_t n_deltas, bool learn_non_evidence, bool noise_aware, bool owners_ok, bool allowed) {
+  return allowed && n_deltas == 1 && !learn_non_evidence && !noise_aware && owners_ok;
+}
+// tiles per block: the format's default or the override (DWX_BLOCK_PULL_TILES, 0 = none) under the format's cap
+constexpr uint64_t bp_block_tiles(bool one_plane, uint64_t override_tiles) {
+  const uint64_t cap = one_plane ? BP1_TILES : BP_TILES, def = one_plane ? BP1_TILES_DEFAULT : BP_TILES;
+  return override_tiles == 0 ? def : override_tiles < cap ? override_tiles : cap;
+}
 // sweep8_kernel<MULTI>: a run of at least this many sweeps over a tile with idle lanes is cut
 // into this many slices per variable
 constexpr uint32_t MULTI_SLICES = 4, MULTI_SLICE_MIN_SWEEPS = 256;

@@ -290,6 +290,8 @@ struct dwx_sampler {
       U32x4 *d_ell = nullptr;
       uint32_t *d_tile0 = nullptr, *d_ov_start = nullptr;
       uint32_t blocks = 0, depth = 0, parts = 0;
+      uint32_t tiles = 0;                 // tiles per block
+      bool one_plane = false;             // one-plane packed rows: pull_ell1_kernel (else pull_ell_kernel)
     };
     std::vector<BlockTable> bp;           // [groups] or empty
     long long *d_bp_qtab = nullptr, *d_bp_partial = nullptr;   // shared: deltas; [max blocks][Wp] sums
@@ -911,10 +913,12 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
   // beyond this the per-chunk tables cost more than they save: such plans keep the
   // per-record atomics and dynamic counts
   uint32_t table_chunks = 4 * MAX_PLAN_BATCHES;
-  uint64_t min_w = 131072, bp_tiles = BP_TILES;   // (fewer weights: the list pull is as fast, tools/tied_sweep.py)
+  uint64_t min_w = 131072, bp_tiles = 0;   // (fewer weights: the list pull is as fast, tools/tied_sweep.py; 0: the row format's block size)
+  bool one_plane_ok = true;                // DWX_BP_TWO_PLANES=1: one-delta tables keep both ballot planes (A/B runs, tests)
   if (const char *e = getenv("DWX_PLAN_TABLE_CHUNKS")) table_chunks = (uint32_t)std::max(1L, atol(e));   // test hooks
   if (const char *e = getenv("DWX_BLOCK_PULL_MIN_W")) min_w = (uint64_t)std::max(0L, atol(e));
-  if (const char *e = getenv("DWX_BLOCK_PULL_TILES")) bp_tiles = (uint64_t)std::min<long>(BP_TILES, std::max(1L, atol(e)));
+  if (const char *e = getenv("DWX_BLOCK_PULL_TILES")) bp_tiles = (uint64_t)std::max(1L, atol(e));   // (capped per format: bp_block_tiles)
+  if (const char *e = getenv("DWX_BP_TWO_PLANES")) one_plane_ok = atol(e) == 0;
   const uint32_t n_chunks = (uint32_t)L->chunks.size();
   L->fast = n_chunks >= 1 && n_chunks <= table_chunks && (uint64_t)n_chunks * c.W * 16 <= ((uint64_t)2 << 30);
   if (batches == 1) L->fast = true;
@@ -946,9 +950,10 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
         if ((!(td.flags & TILE_PULL) && !unary_only) || (td.flags & TILE_OUTSIDE)) continue;
         tile_info[ti] = group_of[ti] | ((unary_only ? 2u : 1u) << 30);   // (the groups cover every tile: the launches do)
       }
+      inc.d_v_init = one_plane_ok ? s->d_v_init : nullptr;   // (input: the signs of one-plane rows)
       devb::build_incidence(s->d_tiles, c.tiles.data(), (uint32_t)c.tiles.size(), tile_info.data(), s->d_v_meta, s->d_v_row,
-                            s->d_row_ptr, s->d_edges, o.learn_non_evidence != 0, o.noise_aware != 0, (uint32_t)c.W, nc, min_w,
-                            (uint32_t)bp_tiles, inc, (void *)s->stream);
+                            s->d_row_ptr, s->d_edges, o.learn_non_evidence != 0, o.noise_aware != 0, (uint32_t)c.W, nc,
+                            min_w, (uint32_t)std::min<uint64_t>(bp_tiles, BP1_TILES), inc, (void *)s->stream);
     } else {
       RawArray<long long> ts;
       hostb::build_static_tables(c, o, groups, ts, &tm, &hm);
@@ -957,7 +962,7 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
       ts.clear();
       lv_step("static tables (host)");
       hostb::Incidence h;
-      hostb::build_incidence(c, o, groups, min_w, bp_tiles, h);
+      hostb::build_incidence(c, o, groups, min_w, bp_tiles, one_plane_ok, h);
       inc.inc_begin = h.inc_begin; inc.inc_end = h.inc_end;
       inc.dvals = h.dvals; inc.max_blocks = h.max_blocks; inc.wp = h.wp;
       try {
@@ -975,6 +980,7 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
           bt.d_ov_start = upload(ovs32, s->stream);
           bt.tile0 = h.bp[k].tile0;
           bt.blocks = h.bp[k].blocks; bt.depth = h.bp[k].depth; bt.total = h.bp[k].total; bt.on_list = h.bp[k].on_list;
+          bt.tiles = h.bp[k].tiles; bt.one_plane = h.bp[k].one_plane;
           rt::stream_sync(s->stream);   // (ovs32 dies with this scope, and the group's rows at once)
           h.bp[k].ell.clear();
         }
@@ -999,13 +1005,15 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
         dwx_sampler::Level::BlockTable &bt = L->bp[k];
         bt.d_tile0 = upload(inc.bp[k].tile0, s->stream);
         bt.blocks = inc.bp[k].blocks; bt.depth = inc.bp[k].depth;
+        bt.tiles = inc.bp[k].tiles; bt.one_plane = inc.bp[k].one_plane;
         // parts per block: one workgroup per CU over all blocks (it owns the CU's whole LDS)
         bt.parts = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rt::cu_count() / bt.blocks, inc.wp / BP_THREADS));
         if (lv_timing)
-          fprintf(stderr, "[dwx block pull] group %u: %u blocks x depth %u (%u entries, %llu bytes of rows), %zu deltas, %llu of %llu entries on the list (%s build)\n",
+          fprintf(stderr, "[dwx block pull] group %u: %u blocks x depth %u (%u entries, %llu bytes of rows), %zu deltas, %llu of %llu entries on the list (%s build), %s rows, %u tiles per block\n",
                   k, bt.blocks, bt.depth, bt.depth * (packed ? BP_PK_ROW : BP_ROW),
                   (unsigned long long)((uint64_t)bt.blocks * bt.depth * inc.wp * (packed ? 8 : 16)), inc.dvals.size(),
-                  (unsigned long long)inc.bp[k].on_list, (unsigned long long)inc.bp[k].total, on_device ? "device" : "host");
+                  (unsigned long long)inc.bp[k].on_list, (unsigned long long)inc.bp[k].total, on_device ? "device" : "host",
+                  bt.one_plane ? "one-plane" : packed ? "two-plane" : "16-byte", bt.tiles);
       }
       std::vector<long long> qtab(inc.dvals.size());
       for (size_t i = 0; i < inc.dvals.size(); ++i) {
@@ -1021,6 +1029,10 @@ dwx_sampler::Level *build_level(dwx_sampler *s, uint32_t batches) {
       rt::allow_dynamic_lds(pull_ell_kernel<2, true, true>, BP_LDS_BYTES);
       rt::allow_dynamic_lds(pull_ell_kernel<3, true, true>, BP_LDS_BYTES);
       rt::allow_dynamic_lds(pull_ell_kernel<4, true, true>, BP_LDS_BYTES);
+      rt::allow_dynamic_lds(pull_ell1_kernel<1>, BP1_LDS_BYTES);
+      rt::allow_dynamic_lds(pull_ell1_kernel<2>, BP1_LDS_BYTES);
+      rt::allow_dynamic_lds(pull_ell1_kernel<3>, BP1_LDS_BYTES);
+      rt::allow_dynamic_lds(pull_ell1_kernel<4>, BP1_LDS_BYTES);
     }
     rt::stream_sync(s->stream);   // (qtab and the tile0 lists die with this scope)
   }
@@ -1247,8 +1259,20 @@ void enqueue_learn_chunk(dwx_sampler *s, uint32_t chunk) {
                  (const uint32_t *)bt->d_tile0, bt->parts, (const long long *)L.d_bp_qtab, L.bp_deltas, L.bp_wp,
                  (const unsigned long long *)s->d_delta, L.d_bp_partial);
     };
+    auto go1 = [&](auto kernel) {
+      rt::launch(kernel, grid, BP_THREADS, BP1_LDS_BYTES, s->stream, (const unsigned long long *)bt->d_ell,
+                 (const uint32_t *)bt->d_tile0, bt->parts, bt->tiles, L.bp_wp, (const unsigned long long *)s->d_delta,
+                 (signed char *)L.d_bp_partial);
+    };
     const bool uni = L.bp_deltas == 1;   // one delta: packed rows of 1 to 4 planes; else 32-bit entries, 1 or 2 rows
-    if (uni) {
+    if (bt->one_plane) {                 // ... with the signs in the rows and one ballot plane in LDS
+      switch (bt->depth) {
+        case 1: go1(pull_ell1_kernel<1>); break;
+        case 2: go1(pull_ell1_kernel<2>); break;
+        case 3: go1(pull_ell1_kernel<3>); break;
+        default: go1(pull_ell1_kernel<4>); break;
+      }
+    } else if (uni) {
       switch (bt->depth) {
         case 1: go(pull_ell_kernel<1, true, true>); break;
         case 2: go(pull_ell_kernel<2, true, true>); break;
@@ -1691,7 +1715,7 @@ int dwx_sampler_create(const dwx_graph *g, const dwx_options *opts, dwx_sampler 
       for (uint64_t i = 0; i < c.W; ++i) w32[i] = (float)c.w_init[i];
       s->d_w32 = upload(w32, st, 1);
       // (+ one variable block of padding: pull_ell_kernel copies whole blocks)
-      const size_t n_delta = c.tiles.size() * 8 + 2 + (size_t)BP_TILES * 8;
+      const size_t n_delta = c.tiles.size() * 8 + 2 + (size_t)BP1_TILES * 8;
       s->d_delta = (unsigned long long *)rt::dmalloc(n_delta * 8);
       rt::dmemset(s->d_delta, 0, n_delta * 8, st);
     }

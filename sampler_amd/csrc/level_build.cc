@@ -260,8 +260,9 @@ void build_static_tables(const CompiledGraph &c, const dwx_options &o, const std
 }
 
 void build_incidence(const CompiledGraph &c, const dwx_options &o, const std::vector<TileGroup> &groups,
-                     uint64_t block_pull_min_w, uint64_t bp_tiles, Incidence &out) {
+                     uint64_t block_pull_min_w, uint64_t bp_tiles, bool allow_one_plane, Incidence &out) {
   const uint32_t nth = host_threads(), nc = (uint32_t)groups.size();
+  std::vector<uint8_t> other_owner(nc, 0);   // per group: an entry's owner is not a boolean evidence variable
   std::vector<uint32_t> chunk_of(c.tiles.size(), 0);
   for (uint32_t k = 0; k < nc; ++k)
     for (uint32_t t = groups[k].t0; t < groups[k].t1; ++t) chunk_of[t] = k;
@@ -290,6 +291,7 @@ void build_incidence(const CompiledGraph &c, const dwx_options &o, const std::ve
               std::memcpy(&miss, &r.aux, 4);
               const float dd = r.fval - miss;    // exact: |hit| == |miss| or one of them is 0
               if (dd == 0.0f) continue;
+              if (((m & VM_CATEGORICAL) || !(m & VM_EVIDENCE)) && !other_owner[chunk_of[ti]]) other_owner[chunk_of[ti]] = 1;
               emit(Inc{r.wid, (uint32_t)(ti * BLOCK_THREADS + l), dd, chunk_of[ti]});
             }
           }
@@ -350,7 +352,9 @@ void build_incidence(const CompiledGraph &c, const dwx_options &o, const std::ve
         const Inc *ent = src->data() + c_start[k];
         const uint64_t n = c_start[k + 1] - c_start[k];
         if (!n) continue;
-        // (1) blocks: runs of <= bp_tiles consecutive tiles, started at tiles that own entries
+        // (1) blocks: runs of <= `tiles` consecutive tiles, started at tiles that own entries
+        const bool one_plane = bp_one_plane(dvals.size(), o.learn_non_evidence != 0, o.noise_aware != 0, !other_owner[k], allow_one_plane);
+        const uint64_t tiles = bp_block_tiles(one_plane, bp_tiles);
         std::fill(has.begin(), has.end(), 0);
         parallel_ranges(n, nth, [&](uint64_t b, uint64_t e) {
           for (uint64_t i = b; i < e; ++i) {   // (test first: the flags are shared by all threads)
@@ -361,7 +365,7 @@ void build_incidence(const CompiledGraph &c, const dwx_options &o, const std::ve
         std::vector<uint32_t> tile0;
         for (uint32_t ti = 0; ti < c.tiles.size(); ++ti) {
           if (!has[ti]) continue;
-          if (tile0.empty() || ti >= tile0.back() + bp_tiles) tile0.push_back(ti);
+          if (tile0.empty() || ti >= tile0.back() + tiles) tile0.push_back(ti);
           block_of[ti] = (uint32_t)tile0.size() - 1;
         }
         const uint64_t nvb = tile0.size();
@@ -391,8 +395,28 @@ void build_incidence(const CompiledGraph &c, const dwx_options &o, const std::ve
             for (uint64_t i = w_at[w]; i < w_at[w + 1]; ++i) {
               const Inc &r = ent[i];
               const uint32_t ti = r.slot / BLOCK_THREADS, vb = block_of[ti];
-              if (vb != cur) { cur = vb; kk = 0; }
-              if (kk < cap && packed) {
+              if (vb != cur) {
+                cur = vb; kk = 0;
+                if (one_plane) {
+                  // the block's row: its first `cap` entries, those that step by +q (v_init != 1) first
+                  uint64_t e1 = i;
+                  uint32_t n_plus = 0;
+                  while (e1 < w_at[w + 1] && e1 - i < cap && block_of[ent[e1].slot / BLOCK_THREADS] == vb) ++e1;
+                  auto plus = [&](const Inc &x) { return c.v_init[c.tiles[x.slot / BLOCK_THREADS].v0 + x.slot % BLOCK_THREADS] != 1u; };
+                  for (uint64_t j = i; j < e1; ++j) n_plus += plus(ent[j]) ? 1u : 0u;
+                  uint32_t at_plus = 0, at_minus = n_plus;
+                  for (uint64_t j = i; j < e1; ++j) {
+                    const Inc &x = ent[j];
+                    const bool p = plus(x);
+                    const uint32_t at = p ? at_plus++ : at_minus++;
+                    unsigned long long &word = ell8[((uint64_t)vb * depth + at / BP_PK_ROW) * Wp + w];
+                    word = bp1_pack_entry(word, at % BP_PK_ROW, (x.slot / BLOCK_THREADS - tile0[vb]) * BLOCK_THREADS + x.slot % BLOCK_THREADS, p);
+                  }
+                }
+              }
+              if (kk < cap && one_plane) {
+                // (written with the block's first entry)
+              } else if (kk < cap && packed) {
                 unsigned long long &word = ell8[((uint64_t)vb * depth + kk / BP_PK_ROW) * Wp + w];
                 word = bp_pack_entry(word, kk % BP_PK_ROW, (ti - tile0[vb]) * BLOCK_THREADS + r.slot % BLOCK_THREADS);
               } else if (kk < cap) {
@@ -430,6 +454,7 @@ void build_incidence(const CompiledGraph &c, const dwx_options &o, const std::ve
         Incidence::BlockTable &bt = out.bp[k];
         bt.tile0.swap(tile0);
         bt.blocks = (uint32_t)nvb; bt.depth = depth;
+        bt.tiles = (uint32_t)tiles; bt.one_plane = one_plane;
         bt.total = n; bt.on_list = ov_count[k];
         max_blocks = std::max(max_blocks, nvb);
       }

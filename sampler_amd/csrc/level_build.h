@@ -54,14 +54,18 @@ struct Incidence {
     std::vector<uint32_t> tile0;                 // [blocks] first tile of every variable block
     std::vector<uint64_t> ov_start;              // [W + 1]: where each weight's leftovers start in the group's list
     uint32_t blocks = 0, depth = 0;              // blocks == 0: the group keeps its whole list
+    uint32_t tiles = 0;                          // tiles per block (bp_block_tiles)
+    bool one_plane = false;                      // the rows are one-plane packed words (device_types.h: bp1_pack_entry)
     uint64_t total = 0, on_list = 0;             // the group's entries; those left on the list
   };
   std::vector<BlockTable> bp;                    // [groups], or empty: no block pull
   std::vector<uint32_t> dvals;                   // ascending f32 bit patterns of the distinct deltas
   uint64_t max_blocks = 0, wp = 0;
 };
+// bp_tiles: tiles per block, 0 = the row format's default; allow_one_plane: groups that qualify (bp_one_plane) take
+// the one-plane rows
 void build_incidence(const CompiledGraph &c, const dwx_options &o, const std::vector<TileGroup> &groups,
-                     uint64_t block_pull_min_w, uint64_t bp_tiles, Incidence &out);
+                     uint64_t block_pull_min_w, uint64_t bp_tiles, bool allow_one_plane, Incidence &out);
 
 // Curvature of the SGD mini-batch of variables [p0, p1) in weight space: max(power-iteration estimate,
 // largest diagonal entry), WITHOUT row_sum_bound's 1.1 safety factor -- the contract of

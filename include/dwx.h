@@ -202,6 +202,15 @@ int dwx_graph_get_positions(const dwx_graph *g, const uint64_t *vids, uint64_t n
  * index_base/index_len[num_values], factor_index[num_index_entries]. */
 int dwx_graph_get_index(const dwx_graph *g, uint64_t *index_base, uint64_t *index_len,
                         uint64_t *factor_index);
+/* Test hook: the compiled workgroup tiles, in device order (tile i of launch l: the launches' tiles follow each
+ * other).  flags are the TILE_* bits of sampler_amd/csrc/device_types.h as the compiler set them (bit 0 SIMPLE,
+ * 1 CATEGORICAL, 2 PULL, 3 TERMS2, 4 INLINE2, 5 GIANT, 6 WIDE, 7 TERMS3, 8 PULL_UNARY, 9 UNIT_ROWS); v0 / nv the
+ * tile's variables as device positions [v0, v0 + nv), nrows its value rows, nedges its edge records.  out[n] with
+ * n == dwx_graph_info.num_tiles (DWX_E_INVALID otherwise).  Host only: no device call. */
+typedef struct dwx_tile_info {
+  uint32_t flags, v0, nv, nrows, nedges;
+} dwx_tile_info;
+int dwx_graph_get_tiles(const dwx_graph *g, uint64_t n, dwx_tile_info *out);
 
 /* ---- sampler (device) -----------------------------------------------------------
  * Replaces GibbsSampler(pfg, weights, numa_nodes, nthread, nodeid, opts)
@@ -564,6 +573,26 @@ int dwx_test_factor_sign(int device, int func, uint64_t arity, const uint8_t *sa
  * (seed = key, variable id = ctr[0..1], sweep = ctr[2..3]). */
 int dwx_test_philox(int device, const uint32_t key[2], const uint32_t ctr[4], uint32_t out[4],
                     double uniforms[2]);
+/* Test hook: the wave-level primitives of the kernels (sampler_amd/csrc/device_intrinsics.h: the gfx950 forms; the
+ * tests' host emulation: its stand-ins), called by ONE workgroup of 256 lanes on the caller's per-lane inputs; every
+ * lane's result comes back.  `in` and `out` are arrays of 8-byte words; n is the number of input words.
+ *   DWX_WAVE_OP_SEG_SUM   in[512]: 256 keys (low 32 bits), 256 int64 addends.  out[512]: per lane the sum from the
+ *                         lane to the end of its run of equal keys inside its wave, then 1 where the lane heads a run
+ *   DWX_WAVE_OP_SUM_F64   in[256] doubles.  out[256]: per lane the sum over its wave (xor-butterfly association)
+ *   DWX_WAVE_OP_BALLOT    in[256] predicates (non-zero = true).  out[256]: the wave's ballot as every lane sees it
+ *   DWX_WAVE_OP_PAIR_SWAP in[256] values (low 32 bits).  out[256]: the value lane ^ 1 passed
+ *   DWX_WAVE_OP_LOAD16 / LOAD8   in[0] = n_rec records of 16 / 8 bytes, in[1 ..]: their bytes (exactly n_rec records
+ *                         are allocated on the device).  K = 12 loads per lane: out[(k * 256 + t) * 2 .. + 2] / out[k *
+ *                         256 + t] = the record lane t got for slot k (record t + 256 k; zeros past the end)
+ *   DWX_WAVE_OP_LOAD_SORTED      in[0] = n_rec, in[1] = first, in[2 ..] the 8-byte records.  K = 4 loads per lane, the
+ *                         workgroup's lanes standing for lanes t < 256 of the sorted sweep: out[k * 256 + t] = record
+ *                         first + t + k * SORT_THREADS (1024), zeros past n_rec
+ * DWX_E_INVALID on an unknown op or a length that does not match. */
+enum {
+  DWX_WAVE_OP_SEG_SUM = 0, DWX_WAVE_OP_SUM_F64 = 1, DWX_WAVE_OP_BALLOT = 2, DWX_WAVE_OP_PAIR_SWAP = 3,
+  DWX_WAVE_OP_LOAD16 = 4, DWX_WAVE_OP_LOAD8 = 5, DWX_WAVE_OP_LOAD_SORTED = 6
+};
+int dwx_test_wave_ops(int device, int op, const uint64_t *in, uint64_t n, uint64_t *out);
 
 #ifdef __cplusplus
 }

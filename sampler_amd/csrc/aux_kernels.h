@@ -4,6 +4,7 @@
 #ifndef DWX_AUX_KERNELS_H_
 #define DWX_AUX_KERNELS_H_
 
+#include "../../include/dwx.h"   // (DWX_WAVE_OP_*: the test hook's op codes)
 #include "tile_walk.h"
 
 namespace dwx {
@@ -806,6 +807,59 @@ __global__ void test_sign_kernel(uint32_t func, uint32_t arity, const VifRec *vi
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     if (arity == 1) out[0] = factor_sign(func, 1, 1u, vifs, assign, 0u, assign[0]);
     else out[0] = factor_sign(func, arity, 0u, vifs, assign, kNoVar, 0u);
+  }
+}
+
+// test hook: the wave-level primitives behind device_intrinsics.h, one workgroup of BLOCK_THREADS lanes on the
+// caller's per-lane inputs (include/dwx.h: dwx_test_wave_ops; tests/test_wave_ops.py).  `op` is uniform: every lane
+// of the workgroup reaches the same primitive together.
+constexpr int WAVE_OP_LOAD_K = (int)STAGE_UNROLL, WAVE_OP_SORT_K = 4;
+__global__ void __launch_bounds__(BLOCK_THREADS)
+test_wave_ops_kernel(uint32_t op, const unsigned long long *in, const void *recs, uint32_t n_rec, uint32_t first,
+                     unsigned long long *out) {
+  const uint32_t t = threadIdx.x;
+  if (op == DWX_WAVE_OP_SEG_SUM) {
+    bool head = false;
+    const long long s = DWX_WAVE_SEG_SUM_I64((uint32_t)in[t], (long long)in[BLOCK_THREADS + t], head);
+    out[t] = (unsigned long long)s;
+    out[BLOCK_THREADS + t] = head ? 1ull : 0ull;
+  } else if (op == DWX_WAVE_OP_SUM_F64) {
+    double v;
+    const unsigned long long bits = in[t];
+    __builtin_memcpy(&v, &bits, 8);
+    const double s = DWX_WAVE_SUM_F64(v);
+    unsigned long long r;
+    __builtin_memcpy(&r, &s, 8);
+    out[t] = r;
+  } else if (op == DWX_WAVE_OP_BALLOT) {
+    out[t] = DWX_BALLOT(in[t] != 0ull);
+  } else if (op == DWX_WAVE_OP_PAIR_SWAP) {
+    out[t] = DWX_PAIR_SWAP_U32((uint32_t)in[t]);
+  } else if (op == DWX_WAVE_OP_LOAD16) {
+    EdgeRec rec[WAVE_OP_LOAD_K];
+    DWX_LOAD_TILE_RECORDS(WAVE_OP_LOAD_K, (const EdgeRec *)recs, n_rec, t, rec);
+#pragma unroll
+    for (int k = 0; k < WAVE_OP_LOAD_K; ++k) {
+      uint32_t fw;
+      __builtin_memcpy(&fw, &rec[k].fval, 4);
+      out[(k * BLOCK_THREADS + t) * 2u] = (unsigned long long)rec[k].wid | ((unsigned long long)rec[k].aux << 32);
+      out[(k * BLOCK_THREADS + t) * 2u + 1u] = (unsigned long long)rec[k].packed | ((unsigned long long)fw << 32);
+    }
+  } else if (op == DWX_WAVE_OP_LOAD8) {
+    EdgeRec8 rec[WAVE_OP_LOAD_K];
+    DWX_LOAD_TILE_RECORDS8(WAVE_OP_LOAD_K, (const EdgeRec8 *)recs, n_rec, t, rec);
+#pragma unroll
+    for (int k = 0; k < WAVE_OP_LOAD_K; ++k) {
+      uint32_t fw;
+      __builtin_memcpy(&fw, &rec[k].f, 4);
+      out[k * BLOCK_THREADS + t] = (unsigned long long)rec[k].key | ((unsigned long long)fw << 32);
+    }
+  } else if (op == DWX_WAVE_OP_LOAD_SORTED) {
+    SortRec8 rec[WAVE_OP_SORT_K];
+    DWX_LOAD_SORTED_RECORDS(WAVE_OP_SORT_K, (const SortRec8 *)recs, n_rec, first, t, rec);
+#pragma unroll
+    for (int k = 0; k < WAVE_OP_SORT_K; ++k)
+      out[k * BLOCK_THREADS + t] = (unsigned long long)rec[k].wid | ((unsigned long long)rec[k].od << 32);
   }
 }
 

@@ -1602,6 +1602,17 @@ int dwx_graph_get_index(const dwx_graph *g, uint64_t *index_base, uint64_t *inde
   return DWX_OK;
 }
 
+int dwx_graph_get_tiles(const dwx_graph *g, uint64_t n, dwx_tile_info *out) {
+  if (!g || (n && !out)) return fail(DWX_E_INVALID, "null argument");
+  const CompiledGraph &c = *g->cg;
+  if (n != c.tiles.size()) return fail(DWX_E_INVALID, "dwx_graph_get_tiles: n is not dwx_graph_info.num_tiles");
+  for (uint64_t i = 0; i < n; ++i) {
+    const TileDesc &t = c.tiles[i];
+    out[i] = dwx_tile_info{t.flags, t.v0, t.nv, t.nrows, t.nedges};
+  }
+  return DWX_OK;
+}
+
 // ------------------------------------------------------------------ sampler
 int dwx_sampler_create(const dwx_graph *g, const dwx_options *opts, dwx_sampler **out) {
   if (!g || !opts || !out) return fail(DWX_E_INVALID, "null argument");
@@ -2746,6 +2757,46 @@ int dwx_test_philox(int device, const uint32_t key[2], const uint32_t ctr[4], ui
     rt::d2h(uniforms, duni, 16, st);
     rt::stream_sync(st);
     rt::dfree(dout); rt::dfree(duni);
+    rt::stream_destroy(st);
+  });
+}
+
+int dwx_test_wave_ops(int device, int op, const uint64_t *in, uint64_t n, uint64_t *out) {
+  if (!in || !out || n == 0) return fail(DWX_E_INVALID, "null argument");
+  uint64_t n_rec = 0, first = 0, head = 0, rec_words = 0, n_out = BLOCK_THREADS;
+  switch (op) {
+    case DWX_WAVE_OP_SEG_SUM: if (n != 2 * BLOCK_THREADS) return fail(DWX_E_INVALID, "dwx_test_wave_ops: 512 input words"); n_out = 2 * BLOCK_THREADS; break;
+    case DWX_WAVE_OP_SUM_F64: case DWX_WAVE_OP_BALLOT: case DWX_WAVE_OP_PAIR_SWAP:
+      if (n != BLOCK_THREADS) return fail(DWX_E_INVALID, "dwx_test_wave_ops: 256 input words");
+      break;
+    case DWX_WAVE_OP_LOAD16: head = 1; rec_words = 2; n_out = (uint64_t)WAVE_OP_LOAD_K * BLOCK_THREADS * 2; break;
+    case DWX_WAVE_OP_LOAD8: head = 1; rec_words = 1; n_out = (uint64_t)WAVE_OP_LOAD_K * BLOCK_THREADS; break;
+    case DWX_WAVE_OP_LOAD_SORTED: head = 2; rec_words = 1; n_out = (uint64_t)WAVE_OP_SORT_K * BLOCK_THREADS; break;
+    default: return fail(DWX_E_INVALID, "dwx_test_wave_ops: unknown op");
+  }
+  if (head) {
+    if (n < head) return fail(DWX_E_INVALID, "dwx_test_wave_ops: input too short");
+    n_rec = in[0];
+    first = head == 2 ? in[1] : 0;
+    if (n_rec > (1u << 20) || first > (1u << 20) || n != head + n_rec * rec_words)
+      return fail(DWX_E_INVALID, "dwx_test_wave_ops: the input does not hold n_rec records");
+  }
+  return guarded([&]() {
+    rt::init_device(device);
+    rt::stream_t st = rt::stream_create();
+    // the records in an allocation of exactly their size: a load past the end would leave it
+    const size_t rec_bytes = (size_t)(n_rec * rec_words * 8), in_bytes = (size_t)((head ? head : n) * 8);
+    unsigned long long *din = (unsigned long long *)rt::dmalloc(in_bytes);
+    void *drec = rt::dmalloc(rec_bytes ? rec_bytes : 16);
+    unsigned long long *dout = (unsigned long long *)rt::dmalloc(n_out * 8);
+    rt::h2d(din, in, in_bytes, st);
+    if (rec_bytes) rt::h2d(drec, in + head, rec_bytes, st);
+    rt::dmemset(dout, 0xEE, n_out * 8, st);
+    rt::launch(test_wave_ops_kernel, 1, BLOCK_THREADS, 0, st, (uint32_t)op, (const unsigned long long *)din,
+               (const void *)drec, (uint32_t)n_rec, (uint32_t)first, dout);
+    rt::d2h(out, dout, n_out * 8, st);
+    rt::stream_sync(st);
+    rt::dfree(din); rt::dfree(drec); rt::dfree(dout);
     rt::stream_destroy(st);
   });
 }

@@ -23,7 +23,7 @@ BUF_WEIGHTS, BUF_GRAD, BUF_ASSIGN_FREE, BUF_ASSIGN_EVID, BUF_TALLIES, BUF_TSTATI
 SYMBOLS = [
     "dwx_last_error", "dwx_version", "dwx_default_options",
     "dwx_graph_create", "dwx_graph_destroy", "dwx_graph_get_info", "dwx_graph_get_schedule",
-    "dwx_graph_get_values", "dwx_graph_get_fixed_point_mask", "dwx_graph_get_positions", "dwx_graph_get_index",
+    "dwx_graph_get_values", "dwx_graph_get_fixed_point_mask", "dwx_graph_get_positions", "dwx_graph_get_index", "dwx_graph_get_tiles",
     "dwx_sampler_create", "dwx_device_init", "dwx_device_count", "dwx_buffer_copy", "dwx_sampler_destroy", "dwx_sample_async", "dwx_sample_n_async", "dwx_sample_sgd_async",
     "dwx_wait", "dwx_sgd_plan", "dwx_sgd_curvature", "dwx_sgd_plan_rows", "dwx_sgd_plan_force_dynamic", "dwx_sgd_get_chunks", "dwx_grad_pack32_async", "dwx_grad_unpack32_async", "dwx_grad_pack_async", "dwx_grad_unpack_async", "dwx_sgd_accumulate_async",
     "dwx_sgd_apply_async", "dwx_sgd_finish",
@@ -33,7 +33,7 @@ SYMBOLS = [
     "dwx_get_assignments", "dwx_set_assignments", "dwx_get_sweep", "dwx_set_sweep",
     "dwx_device_buffer", "dwx_halo_create", "dwx_halo_destroy", "dwx_halo_buffer", "dwx_halo_message_bytes", "dwx_halo_pack_async",
     "dwx_halo_unpack_async", "dwx_stream", "dwx_kernel_time", "dwx_kernel_time_reset",
-    "dwx_test_factor_sign", "dwx_test_philox",
+    "dwx_test_factor_sign", "dwx_test_philox", "dwx_test_wave_ops",
 ]
 
 
@@ -72,6 +72,13 @@ class GraphInfo(C.Structure):
         ("max_super_tile_variables", C.c_uint64)]
 
 
+# TileDesc::flags (sampler_amd/csrc/device_types.h)
+TILE_SIMPLE, TILE_CATEGORICAL, TILE_PULL, TILE_TERMS2, TILE_INLINE2, TILE_GIANT, TILE_WIDE, TILE_TERMS3, TILE_PULL_UNARY, TILE_UNIT_ROWS = (1 << i for i in range(10))
+# dwx_tile_info (include/dwx.h), as a numpy record
+TILE_DTYPE = np.dtype([("flags", np.uint32), ("v0", np.uint32), ("nv", np.uint32), ("nrows", np.uint32), ("nedges", np.uint32)])
+WAVE_OP_SEG_SUM, WAVE_OP_SUM_F64, WAVE_OP_BALLOT, WAVE_OP_PAIR_SWAP, WAVE_OP_LOAD16, WAVE_OP_LOAD8, WAVE_OP_LOAD_SORTED = range(7)
+
+
 class Options(C.Structure):
     _fields_ = [("device", C.c_int32), ("sample_evidence", C.c_int32),
                 ("learn_non_evidence", C.c_int32), ("noise_aware", C.c_int32),
@@ -103,6 +110,7 @@ class Library:
         L.dwx_graph_get_index.argtypes = [vp, vp, vp, vp]
         L.dwx_graph_get_positions.argtypes = [vp, vp, u64, vp]
         L.dwx_graph_get_fixed_point_mask.argtypes = [vp, vp]
+        L.dwx_graph_get_tiles.argtypes = [vp, u64, vp]
         L.dwx_sampler_create.argtypes = [vp, vp, vp]
         L.dwx_device_init.argtypes = [C.c_int32]
         L.dwx_device_count.argtypes = [vp]
@@ -150,6 +158,7 @@ class Library:
         L.dwx_kernel_time_reset.argtypes = [vp, i32]
         L.dwx_test_factor_sign.argtypes = [i32, i32, u64, vp, vp]
         L.dwx_test_philox.argtypes = [i32, vp, vp, vp, vp]
+        L.dwx_test_wave_ops.argtypes = [i32, i32, vp, u64, vp]
 
     def check(self, rc):
         if rc != DWX_OK:
@@ -161,6 +170,14 @@ class Library:
         out, uni = np.zeros(4, np.uint32), np.zeros(2, np.float64)
         self.check(self.L.dwx_test_philox(device, k.ctypes.data, c.ctypes.data, out.ctypes.data, uni.ctypes.data))
         return out, uni
+
+    def test_wave_ops(self, op, words, n_out, device=0):
+        """dwx_test_wave_ops: one workgroup of 256 lanes calls the primitive `op` (WAVE_OP_*) on `words` (uint64,
+        the layout include/dwx.h gives per op) -> uint64[n_out], every lane's result."""
+        w = np.ascontiguousarray(words, np.uint64)
+        out = np.zeros(n_out, np.uint64)
+        self.check(self.L.dwx_test_wave_ops(device, int(op), w.ctypes.data, len(w), out.ctypes.data))
+        return out
 
     def test_factor_sign(self, func, sat, device=0):
         sat = np.ascontiguousarray(sat, np.uint8)
@@ -211,6 +228,13 @@ class Graph:
         m = np.zeros(self.info.num_variables, np.uint8)
         self.lib.check(self.lib.L.dwx_graph_get_fixed_point_mask(self.h, m.ctypes.data))
         return m
+
+    def tiles(self):
+        """The compiled workgroup tiles in device order (dwx_graph_get_tiles): a numpy record array with the
+        fields flags (TILE_* bits), v0, nv, nrows, nedges."""
+        out = np.zeros(self.info.num_tiles, TILE_DTYPE)
+        self.lib.check(self.lib.L.dwx_graph_get_tiles(self.h, len(out), out.ctypes.data))
+        return out
 
     def positions(self, vids):
         vids = np.ascontiguousarray(vids, np.uint64)

@@ -113,6 +113,10 @@ typedef struct dwx_compile_opts {
                                   max_records_per_weight (they read 0: "nothing is known, send int64") -- a
                                   pass over every record with a histogram per weight that only multi-GPU
                                   drivers need; `dw gibbs` on one GPU sets it (2 s at config 5's size)      */
+  uint32_t keep_factors;       /* 1: also keep a factor-major table (16 bytes per factor, 8 per edge of a factor
+                                  of arity >= 2, 8 more per factor where a feature value is no exact f32;
+                                  dwx_graph_info.factor_table_bytes) -- what dwx_score / dwx_trace_score read.
+                                  Changes nothing else the compiler produces.  Default 0: nothing is kept    */
 } dwx_compile_opts;
 
 typedef struct dwx_graph_info {
@@ -141,6 +145,8 @@ typedef struct dwx_graph_info {
    * grad_shift == 0: nothing is known (categorical variables, non-unary factors): send int64. */
   uint64_t grad_shift, grad_unit_max, max_records_per_weight;
   uint64_t max_super_tile_variables; /* variables of the largest weight-sorted super-tile (0: no sorted copy) */
+  uint64_t factor_table_bytes; /* the factor-major table of dwx_compile_opts.keep_factors (0 without): host bytes,
+                                  and device bytes once dwx_score / dwx_trace_score has run; NOT in device_bytes */
 } dwx_graph_info;
 
 /* Runtime options of one sampler (the CmdParser fields the hot path reads:
@@ -460,6 +466,36 @@ int dwx_trace_diagnostics(dwx_sampler *s, uint32_t max_lag, double rhat_threshol
  * it. */
 int dwx_trace_cooccurrence(dwx_sampler *s, const uint64_t *rows_a, const uint64_t *rows_b, uint64_t n_pairs,
                            uint64_t first_entry, uint64_t n_entries, uint64_t *n_ab, uint64_t *n_a, uint64_t *n_b);
+/* Joint log-score of a state under the model, computed on the device.  The reference has no counterpart beyond the
+ * per-variable sum FactorGraph::potential (src/factor_graph.h:127-145), which this extends to ALL factors.
+ * Definition.  For a joint assignment x (dense values, as dwx_get_assignments / dwx_trace_read give them):
+ *   score(x) = sum over f of  w[weight_id_f] * (sign_f(x) * feature_value_f)
+ * over ALL factors of the graph (those on fixed weights and on evidence variables included); sign_f is the factor
+ * function of src/factor.h:112-299 with no variable proposed; w is the f64 master weights (DWX_BUF_WEIGHTS) at the
+ * time of the call -- the weights a run dumps.  score(x) is the log of the unnormalised probability; the partition
+ * function is not estimated.
+ * Numerics (independent of kernels, grid sizes and the order of atomics):  t_f = w * (s * fval), two f64
+ * multiplications in that association, no contraction;  q_f = llrint(2^32 * t_f) (round-to-nearest-even);  the q_f are
+ * summed EXACTLY (q >> 32 into a signed 64-bit sum, the low 32 bits into an unsigned one: F < 2^32, neither can
+ * overflow);  the result is (double)(((__int128)hi << 32) + lo) * 2^-32: the correctly rounded value of the exact
+ * integer sum over 2^32, also where that sum is beyond int64.  A term that is not finite or has |t_f| >= 2^30 makes the
+ * call fail with DWX_E_LIMIT, the outputs left as they were.  (RATIO at arity >= 3 takes log2 of 3, 4, ... on the
+ * device: its sign is the device's f64 log2, within 1 ulp of the true value.)
+ *   dwx_score        the score of a live chain (chain as in dwx_get_assignments: 0 free, 1 evidence); deferred draws
+ *                    (dwx_kernel_time, kind 7) are run first, exactly as dwx_get_assignments does; ghost variables'
+ *                    assignments are read like any other.
+ *   dwx_trace_score  scores[e] of entries [first_entry, first_entry + n_entries) of the sample trace, entry 0 the
+ *                    oldest held (as dwx_trace_read); best_entry (may be null): the entry of the range with the largest
+ *                    score, the OLDEST on a tie.  n_entries == 0 is DWX_OK, *best_entry = UINT64_MAX.
+ * Both need a graph compiled with dwx_compile_opts.keep_factors; the device copy of its factor table is uploaded by
+ * the first call and freed by dwx_sampler_destroy (DWX_E_NOMEM there, or for the call's few temporary bytes, leaves
+ * the sampler usable).  Both are ordered after everything queued on the sampler's stream, return when done and change
+ * nothing of the sampler's state (sweep counter, chains, tallies, RB sums, trace).  A graph without factors scores 0.
+ * DWX_E_INVALID: the graph was compiled without keep_factors; a null output; a chain other than 0 / 1;
+ * dwx_trace_score: trace never enabled, a range outside the entries held, a graph with ghost variables (they are not
+ * traced).  With neither function ever called nothing is allocated or launched. */
+int dwx_score(dwx_sampler *s, int chain, double *score);
+int dwx_trace_score(dwx_sampler *s, uint64_t first_entry, uint64_t n_entries, double *scores, uint64_t *best_entry);
 /* assignments_free (chain 0) / assignments_evid (chain 1), original variable order */
 int dwx_get_assignments(dwx_sampler *s, int chain, uint64_t *out);
 int dwx_set_assignments(dwx_sampler *s, int chain, const uint64_t *in);

@@ -788,6 +788,195 @@ trace_cooc_kernel(const unsigned long long *ring, uint32_t words, uint32_t cap, 
   }
 }
 
+// dwx_score / dwx_trace_score: the joint log-score of a state, sum over ALL factors of w * (sign * fval), from the
+// factor-major table (CompiledGraph::frecs; include/dwx.h states the definition, DESIGN.md 3.1j the layout).  The
+// reference has the per-variable sum only (FactorGraph::potential, src/factor_graph.h:127-145).
+//
+// Every one of the ten functions (src/factor.h:112-299) is a function of the arity, the number nb of satisfied BODY
+// positions (all but the last) and whether the head (the last) is satisfied -- what a lane can keep per entry while
+// it walks a factor's positions once for several entries.  Agrees with factor_sign for every function and arity
+// (arity 0, which factor_sign never meets: the functions on no predicates, head false).
+DWX_DEV double sign_from_counts(uint32_t func, uint32_t arity, uint32_t nb, bool head) {
+  if (arity == 1u) return unary_sign(func, head);
+  const uint32_t body = arity ? arity - 1u : 0u;
+  switch (func) {
+    case FUNC_AND: case FUNC_ISTRUE: return (nb == body && (head || !arity)) ? 1.0 : -1.0;
+    case FUNC_AND_CATEGORICAL: return (nb == body && (head || !arity)) ? 1.0 : 0.0;
+    case FUNC_OR: return (nb > 0u || head) ? 1.0 : -1.0;
+    case FUNC_EQUAL: { const uint32_t k = nb + (head ? 1u : 0u); return (k == 0u || k == arity) ? 1.0 : -1.0; }
+    case FUNC_IMPLY_MLN: return (nb != body || head) ? 1.0 : 0.0;
+    case FUNC_IMPLY_NATURAL: return nb != body ? 0.0 : (head ? 1.0 : -1.0);
+    default: {  // LINEAR, RATIO, LOGICAL: the body positions b with !b || head
+      const uint32_t count = head ? body : body - nb;
+      if (func == FUNC_LINEAR) return (double)count;
+      if (func == FUNC_RATIO) return log2(1.0 + (double)count);
+      return count > 0u ? 1.0 : 0.0;
+    }
+  }
+}
+
+// One term into a lane's exact sum: q = llrint(2^32 t) (the scaling is exact, the rounding to nearest-even), its
+// arithmetic high part into hi, its low 32 bits into lo -- fewer than 2^32 terms: neither can overflow.
+constexpr double SCORE_SCALE = 4294967296.0, SCORE_TERM_LIMIT = 1073741824.0;   // 2^32; |t| < 2^30
+DWX_DEV void score_term(double t, long long &hi, unsigned long long &lo, bool &bad) {
+  if (!(fabs(t) < SCORE_TERM_LIMIT)) { bad = true; return; }   // (NaN fails the comparison too)
+  const long long q = llrint(t * SCORE_SCALE);
+  hi += q >> 32;
+  lo += (unsigned long long)(uint32_t)q;
+}
+
+// Where a position's value comes from.  MODE 0: a live chain, assign[p] (EB = 1).  MODE 1 / 8: the trace ring at a
+// bit / a byte per position; a pass covers EB consecutive entries, entry u in plane (slot0 + u) mod cap; entries
+// u >= ne (the last pass of a call) read plane slot0 again and are dropped at the end.
+#ifndef DWX_SCORE_EB
+#define DWX_SCORE_EB 8
+#endif
+constexpr int SCORE_EB = DWX_SCORE_EB;
+#ifndef DWX_SCORE_MAX_BLOCKS
+#define DWX_SCORE_MAX_BLOCKS 1024
+#endif
+constexpr uint32_t SCORE_MAX_BLOCKS = DWX_SCORE_MAX_BLOCKS;   // the grid's cap: four workgroups per CU walk the same few planes
+template <int MODE, int EB>
+struct ScoreReader {
+  const unsigned char *plane[EB];
+  DWX_DEV ScoreReader(const void *src, uint32_t words, uint32_t cap, uint32_t slot0, uint32_t ne) {
+#pragma unroll
+    for (int u = 0; u < EB; ++u) {
+      uint32_t su = slot0;
+      if (MODE != 0 && (uint32_t)u < ne) {        // (slot0 < cap, u < ne <= cap: one wrap at the most)
+        su = slot0 + (uint32_t)u;
+        if (su >= cap) su -= cap;
+      }
+      plane[u] = (const unsigned char *)src + (MODE == 0 ? (size_t)0 : (size_t)su * words * 8u);
+    }
+  }
+  // the EB gathers of one position, issued together
+  DWX_DEV void sat(const VifRec vf, bool (&s)[EB]) const {
+    uint32_t x[EB];
+#pragma unroll
+    for (int u = 0; u < EB; ++u) {
+      if (MODE == 0) x[u] = ((const uint32_t *)plane[u])[vf.vid];
+      else if (MODE == 1) x[u] = (((const uint32_t *)plane[u])[vf.vid >> 5] >> (vf.vid & 31u)) & 1u;   // (little-endian: bit p of the plane)
+      else x[u] = plane[u][vf.vid];
+    }
+#pragma unroll
+    for (int u = 0; u < EB; ++u) s[u] = x[u] == vf.equal_to;
+  }
+};
+
+// The lanes' sums of a workgroup into acc[2u], acc[2u + 1] (hi, lo of entry u < ne): per wave with the segmented
+// sum over one run (all 64 lanes reach it), across waves through LDS, then ONE atomic pair per workgroup and entry.
+// Integer sums: the result does not depend on the grid or on the order of the atomics.
+template <int EB>
+DWX_DEV void score_reduce(const long long (&hi)[EB], const unsigned long long (&lo)[EB], bool bad, uint32_t ne,
+                          unsigned long long *acc, unsigned *flag) {
+  __shared__ unsigned long long s_part[BLOCK_THREADS / 64u][2 * EB];
+  const uint32_t t = threadIdx.x, wave = t >> 6;
+#pragma unroll
+  for (int u = 0; u < EB; ++u) {
+    bool head = false;
+    const long long h = DWX_WAVE_SEG_SUM_I64(0u, hi[u], head);
+    const long long l = DWX_WAVE_SEG_SUM_I64(0u, (long long)lo[u], head);
+    if ((t & 63u) == 0u) { s_part[wave][2 * u] = (unsigned long long)h; s_part[wave][2 * u + 1] = (unsigned long long)l; }
+  }
+  if (bad) atomicAdd(flag, 1u);
+  __syncthreads();
+  if (t < 2u * ne) {
+    unsigned long long sum = 0;
+    for (uint32_t w = 0; w < BLOCK_THREADS / 64u; ++w) sum += s_part[w][t];
+    if (sum) atomicAdd(&acc[t], sum);
+  }
+}
+
+// A LANE OWNS A FACTOR, grid-stride over the table: the 16-byte records are one coalesced stream, a factor's entries
+// 8-byte loads at consecutive addresses from lane to lane where arities agree, and every position's value EB
+// independent gathers (trace_cooc_kernel's pattern: the waves resident together read the same few planes, which
+// stay in L2 meanwhile).  Factors wider than SCORE_WAVE_ARITY are score_wide_kernel's.  No wave operation inside
+// the loop: lanes may leave it at different times.
+template <int MODE, int EB>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+score_kernel(const FactorRec *recs, const double *fval64, const VifRec *vifs, uint32_t n_factors, const double *weights,
+             const void *src, uint32_t words, uint32_t cap, uint32_t slot0, uint32_t ne, unsigned long long *acc,
+             unsigned *flag) {
+  const ScoreReader<MODE, EB> rd(src, words, cap, slot0, ne);
+  long long hi[EB];
+  unsigned long long lo[EB];
+#pragma unroll
+  for (int u = 0; u < EB; ++u) { hi[u] = 0; lo[u] = 0; }
+  bool bad = false;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t f = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; f < n_factors; f += stride) {
+    const FactorRec r = recs[f];
+    const uint32_t func = r.packed & FREC_FUNC_MASK, field = r.packed >> FREC_ARITY_SHIFT;
+    const uint32_t arity = (r.packed & FREC_UNARY) ? 1u : field;
+    if (arity > SCORE_WAVE_ARITY) continue;
+    uint32_t nb[EB];
+    bool head[EB], s[EB];
+#pragma unroll
+    for (int u = 0; u < EB; ++u) { nb[u] = 0; head[u] = false; }
+    if (r.packed & FREC_UNARY) {
+      rd.sat(VifRec{r.aux, field}, head);
+    } else {
+      const VifRec *v = vifs + r.aux;
+      for (uint32_t i = 0; i + 1u < arity; ++i) {
+        rd.sat(v[i], s);
+#pragma unroll
+        for (int u = 0; u < EB; ++u) nb[u] += s[u] ? 1u : 0u;
+      }
+      if (arity) rd.sat(v[arity - 1u], head);
+    }
+    const double fv = (r.packed & FREC_F64_FLAG) ? fval64[f] : (double)r.fval;
+    const double w = weights[r.wid];
+#pragma unroll
+    for (int u = 0; u < EB; ++u) score_term(w * (sign_from_counts(func, arity, nb[u], head[u]) * fv), hi[u], lo[u], bad);
+  }
+  score_reduce<EB>(hi, lo, bad, ne, acc, flag);
+}
+
+// A WAVE OWNS A WIDE FACTOR (arity > SCORE_WAVE_ARITY; wide[] lists them): lanes take its positions strided and
+// count their satisfied body positions, one segmented sum per entry yields nb and the head (packed: head << 32 |
+// nb), lane 0 evaluates the function and keeps the term.  The waves' loop over the list has the same trip count in
+// all 64 lanes; no ballot (arities differ from wave to wave).
+template <int MODE, int EB>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+score_wide_kernel(const FactorRec *recs, const double *fval64, const VifRec *vifs, const uint32_t *wide, uint32_t n_wide,
+                  const double *weights, const void *src, uint32_t words, uint32_t cap, uint32_t slot0, uint32_t ne,
+                  unsigned long long *acc, unsigned *flag) {
+  const ScoreReader<MODE, EB> rd(src, words, cap, slot0, ne);
+  long long hi[EB];
+  unsigned long long lo[EB];
+#pragma unroll
+  for (int u = 0; u < EB; ++u) { hi[u] = 0; lo[u] = 0; }
+  bool bad = false;
+  const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (BLOCK_THREADS / 64u);
+  for (uint32_t i = blockIdx.x * (BLOCK_THREADS / 64u) + (threadIdx.x >> 6); i < n_wide; i += waves) {
+    const uint32_t f = wide[i];
+    const FactorRec r = recs[f];
+    const uint32_t func = r.packed & FREC_FUNC_MASK, arity = r.packed >> FREC_ARITY_SHIFT;
+    const VifRec *v = vifs + r.aux;
+    long long cnt[EB];
+    bool s[EB];
+#pragma unroll
+    for (int u = 0; u < EB; ++u) cnt[u] = 0;
+    for (uint32_t j = lane; j < arity; j += 64u) {
+      rd.sat(v[j], s);
+      const long long one = j + 1u == arity ? (1ll << 32) : 1ll;
+#pragma unroll
+      for (int u = 0; u < EB; ++u) cnt[u] += s[u] ? one : 0ll;
+    }
+    const double fv = (r.packed & FREC_F64_FLAG) ? fval64[f] : (double)r.fval;
+    const double w = weights[r.wid];
+#pragma unroll
+    for (int u = 0; u < EB; ++u) {
+      bool first = false;
+      const long long c = DWX_WAVE_SEG_SUM_I64(0u, cnt[u], first);
+      if (lane == 0u)
+        score_term(w * (sign_from_counts(func, arity, (uint32_t)c, (c >> 32) != 0) * fv), hi[u], lo[u], bad);
+    }
+  }
+  score_reduce<EB>(hi, lo, bad, ne, acc, flag);
+}
+
 // test hook: the raw Philox4x32-10 block function and the two uniforms drawn from it, on the
 // device (Random123 known-answer vectors; tests/test_philox_kat.py)
 __global__ void test_philox_kernel(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,

@@ -130,6 +130,26 @@ struct alignas(8) VifRec {
   uint32_t equal_to;  // dense predicate value
 };
 
+// One factor of the factor-major table (dwx_compile_opts.keep_factors; score_kernel): the only view of the
+// graph that holds each factor ONCE -- the edge records above hold it once per value row that names it.
+//   packed: bits 0-3 func id, bit 4: feature value needs the f64 side array (indexed by factor id),
+//           bit 5 FREC_UNARY: arity 1 with its entry in the record itself -- bits 8-31 the dense equal_to,
+//           aux the variable's device position; else bits 8-31 the arity (0 included) and aux the base
+//           of the factor's entries, in its own edge order (the head of an implication last), in the
+//           table's VifRec array
+struct alignas(16) FactorRec {
+  uint32_t wid, packed, aux;
+  float fval;
+};
+static_assert(sizeof(FactorRec) == 16, "FactorRec must be 16 bytes");
+constexpr uint32_t FREC_FUNC_MASK = 0xF, FREC_F64_FLAG = 1u << 4, FREC_UNARY = 1u << 5;
+constexpr uint32_t FREC_ARITY_SHIFT = 8, FREC_ARITY_MAX = (1u << 24) - 1;
+// factors up to this arity are evaluated by a lane each, wider ones by a wave each (score_wide_kernel)
+#ifndef DWX_SCORE_WAVE_ARITY
+#define DWX_SCORE_WAVE_ARITY 64
+#endif
+constexpr uint32_t SCORE_WAVE_ARITY = DWX_SCORE_WAVE_ARITY;
+
 // One workgroup tile: a run of consecutive variables (device order) of one colour and
 // one type whose value rows and edge records fit the LDS budget -- or ONE oversized
 // variable (rows > rcap or edges > ecap), processed straight from HBM.

@@ -45,7 +45,7 @@ const FlagSpec kFlags[] = {
     {"", "gpus", true}, {"", "devices", true}, {"", "comm", true}, {"", "rao_blackwell", false},
     {"", "trace", true}, {"", "trace_vars", true},
     {"", "diagnostics", false}, {"", "diag_max_lag", true}, {"", "diag_rhat", true},
-    {"", "trace_pairs", true},
+    {"", "trace_pairs", true}, {"", "trace_score", false}, {"", "map", false},
 };
 
 const FlagSpec *find_flag(const std::string &tok) {
@@ -188,6 +188,8 @@ CmdLine parse_cmdline(int argc, const char *const argv[]) {
     else if (n == "diag_max_lag") { if (need_u()) a.diag_max_lag = u; }
     else if (n == "diag_rhat") { if (need_d()) a.diag_rhat = d; }
     else if (n == "trace_pairs") a.trace_pairs = val;
+    else if (n == "trace_score") a.trace_score = true;
+    else if (n == "map") a.map = true;
     else if (n == "comm") {
       if (val != "rccl" && val != "host") { ++a.num_errors; err << "PARSE ERROR: Argument: --comm\n             must be rccl or host\n"; }
       a.comm = val;
@@ -206,6 +208,8 @@ CmdLine parse_cmdline(int argc, const char *const argv[]) {
   if (is_gibbs && !have_i) { ++a.num_errors; err << "PARSE ERROR:\n             Required argument missing: n_inference_epoch\n"; }
   if (a.diagnostics && !a.trace) { ++a.num_errors; err << "PARSE ERROR: Argument: --diagnostics\n             needs --trace N: the diagnostics are computed over the sample trace\n"; }
   if (a.diagnostics && (a.diag_max_lag < 1 || a.diag_max_lag > 64)) { ++a.num_errors; err << "PARSE ERROR: Argument: --diag_max_lag\n             must be 1 .. 64\n"; }
+  if (a.trace_score && !a.trace) { ++a.num_errors; err << "PARSE ERROR: Argument: --trace_score\n             needs --trace N: the scores are those of the sample trace's entries\n"; }
+  if (a.map && !a.trace) { ++a.num_errors; err << "PARSE ERROR: Argument: --map\n             needs --trace N: the best joint state is taken from the sample trace\n"; }
   if (!a.trace_pairs.empty() && !a.trace) { ++a.num_errors; err << "PARSE ERROR: Argument: --trace_pairs\n             needs --trace N: the joint counts are taken over the sample trace\n"; }
   // XXX hack of the reference to support two step-size flags (src/cmd_parser.cc:158-160)
   if (a.stepsize == 0.01) a.stepsize = a.stepsize2;
@@ -254,6 +258,8 @@ std::ostream &operator<<(std::ostream &stream, const CmdLine &args) {
       {"diag_max_lag", [](std::ostream &o, const CmdLine &a) { o << a.diag_max_lag; }, [](const CmdLine &a) { return a.diagnostics; }},
       {"diag_rhat", [](std::ostream &o, const CmdLine &a) { o << a.diag_rhat; }, [](const CmdLine &a) { return a.diagnostics; }},
       {"trace_pairs", [](std::ostream &o, const CmdLine &a) { o << a.trace_pairs; }, [](const CmdLine &a) { return !a.trace_pairs.empty(); }},
+      {"trace_score", [](std::ostream &o, const CmdLine &a) { o << a.trace_score; }, [](const CmdLine &a) { return a.trace_score; }},
+      {"map", [](std::ostream &o, const CmdLine &a) { o << a.map; }, [](const CmdLine &a) { return a.map; }},
   };
 #undef DWX_ROW
 #undef DWX_ROW_LIST
@@ -1066,6 +1072,51 @@ void dump_pairs_to_file(const std::string &path, dwx_sampler *sampler, const Tra
   if (!f) throw std::runtime_error("cannot write " + path);
 }
 
+// --trace_score / --map: the joint log-score of every entry the ring holds, summed on the device (dwx_trace_score), and
+// the best entry's assignment (dwx_trace_read of that one entry)
+void dump_scores_to_file(const std::string &score_path, const std::string &map_path, const LoadedGraph &g, dwx_sampler *sampler,
+                         const uint64_t *var_val_base, const uint64_t *value_sparse) {
+  auto ok = [](int rc) { if (rc != DWX_OK) throw std::runtime_error(dwx_last_error()); };
+  uint64_t count = 0, best = ~0ull;
+  ok(dwx_trace_info(sampler, &count, nullptr, nullptr));
+  std::vector<uint64_t> ids(count);
+  std::vector<double> scores(count);
+  ok(dwx_trace_info(sampler, nullptr, nullptr, ids.data()));
+  ok(dwx_trace_score(sampler, 0, count, scores.data(), &best));
+  auto write = [](const std::string &path, const std::string &s) {
+    std::ofstream f(path, std::ios::binary);
+    f.write(s.data(), (std::streamsize)s.size());
+    if (!f) throw std::runtime_error("cannot write " + path);
+  };
+  char num[64];
+  if (!score_path.empty()) {
+    std::string s = "# entries=" + std::to_string(count);
+    if (count) {
+      snprintf(num, sizeof num, "%.17g", scores[best]);
+      s += " best_sweep=" + std::to_string(ids[best]) + " best_score=" + num;
+    }
+    s.push_back('\n');
+    for (uint64_t e = 0; e < count; ++e) {
+      snprintf(num, sizeof num, "%.17g", scores[e]);
+      append_u64(s, ids[e]); s.push_back(' '); s += num; s.push_back('\n');
+    }
+    write(score_path, s);
+  }
+  if (!map_path.empty()) {
+    std::string s;
+    if (count) {
+      const uint64_t V = g.n_variables;
+      std::vector<uint8_t> x(V);
+      ok(dwx_trace_read(sampler, best, 1, nullptr, 0, x.data()));
+      for (uint64_t v = 0; v < V; ++v) {
+        append_u64(s, v); s.push_back(' ');
+        append_u64(s, g.var_dtype[v] == 0 ? (uint64_t)x[v] : value_sparse[var_val_base[v] + x[v]]); s.push_back('\n');
+      }
+    }
+    write(map_path, s);
+  }
+}
+
 // Graph-compile options of a `dw gibbs` run.  Ordering the variables of an all-unary graph by the
 // weight of their first record makes a sweep ~5 % faster and the host-side build
 // much slower -- the records are then gathered in a random order: 10 s of a 42 s run at config 5's
@@ -1081,6 +1132,8 @@ dwx_compile_opts compile_opts_for(const CmdLine &args) {
   co.no_weight_order = order ? 0u : 1u;
   // (what the gradient all-reduce may assume about the sums: only runs over several GPUs ask)
   co.no_narrow_info = (args.gpus >= 2 || args.n_datacopy > 1) ? 0u : 1u;
+  // (the factor-major table: only runs that score ask)
+  co.keep_factors = (args.trace_score || args.map) ? 1u : 0u;
   return co;
 }
 
@@ -1349,6 +1402,17 @@ int gibbs(const CmdLine &args) {
         std::cout << "DUMPING... TEXT    : " << fn << std::endl;
         dump_pairs_to_file(fn, sampler, pairs);
         phase("dump pairs");
+      }
+      if (args.trace_score || args.map) {
+        // --trace_score: "# entries=<n> best_sweep=<id> best_score=<s>", then "sweep_id score" per entry, oldest first;
+        // --map: "vid value" of the best entry.  The reference has the per-variable sum FactorGraph::potential only
+        // (src/factor_graph.h:127-145).
+        const std::string fs = args.trace_score ? args.output_folder + "/inference_result.out.score.text" : std::string();
+        const std::string fm = args.map ? args.output_folder + "/inference_result.out.map.text" : std::string();
+        if (args.trace_score) std::cout << "DUMPING... TEXT    : " << fs << std::endl;
+        if (args.map) std::cout << "DUMPING... TEXT    : " << fm << std::endl;
+        dump_scores_to_file(fs, fm, lg, sampler, base.data(), sparse.data());
+        phase("dump scores");
       }
       if (progress) {
         // the reference's closing calibration table (InferenceResult::show_marginal_histogram,

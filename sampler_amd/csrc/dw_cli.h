@@ -52,6 +52,10 @@ struct CmdLine {
   double diag_rhat = 1.01;      // <out>/inference_result.out.diagnostics.text; --diag_rhat: the summary's threshold
   std::string trace_pairs;      // --trace_pairs FILE (with --trace): joint counts of the listed (variable, value) pairs over the
                                 // trace, counted on the device (dwx_trace_cooccurrence), to <out>/inference_result.out.pairs.text
+  bool trace_score = false;     // --trace_score (with --trace): the joint log-score of every entry of the trace, summed on
+                                // the device (dwx_trace_score), to <out>/inference_result.out.score.text
+  bool map = false;             // --map (with --trace): the entry with the largest score as "vid value" lines, to
+                                // <out>/inference_result.out.map.text
   int num_errors = 0;
   std::string error_text;
 };
@@ -125,6 +129,13 @@ TracePairs load_trace_pairs(const std::string &file, const LoadedGraph &g, const
                             const uint64_t *value_sparse);
 // "# entries=<n>" then "vid_a value_a vid_b value_b n_ab n_a n_b" per pair, in input order, over all entries held
 void dump_pairs_to_file(const std::string &path, dwx_sampler *sampler, const TracePairs &pairs);
+
+// --trace_score / --map (dw_cli.cc): the scores of all entries held (dwx_trace_score).  score_path (if not empty):
+// "# entries=<n> best_sweep=<id> best_score=<%.17g>", then "sweep_id score" (%.17g) per entry, oldest first.  map_path
+// (if not empty): "vid value" of every variable in the best entry (the oldest on a tie), in id order, values as the
+// marginals dump prints them (the sparse domain value of a categorical variable).
+void dump_scores_to_file(const std::string &score_path, const std::string &map_path, const LoadedGraph &g, dwx_sampler *sampler,
+                         const uint64_t *var_val_base, const uint64_t *value_sparse);
 
 // graph-compile options of a run (dw_cli.cc: the weight order of the variables only for long runs)
 dwx_compile_opts compile_opts_for(const CmdLine &args);

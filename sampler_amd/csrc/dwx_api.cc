@@ -241,6 +241,13 @@ struct dwx_sampler {
   uint32_t trace_next = 0, trace_count = 0;                  // the plane the next sweep writes; entries held
   bool trace_on = false;                   // inference sweeps record
   std::vector<uint64_t> trace_ids;         // [trace_cap] by plane: the sweep counter its entry was drawn at
+  // Joint log-score (dwx_score, dwx_trace_score): the device copy of the graph's factor-major table,
+  // uploaded by the first call
+  FactorRec *d_frecs = nullptr;
+  VifRec *d_fvifs = nullptr;
+  double *d_ffval64 = nullptr;
+  uint32_t *d_fwide = nullptr;
+  bool score_ready = false;
   long long *d_pot = nullptr;       // [V] fixed-point sums by device position (allocated on first use)
   int pot_alloc = 0;                // 0 not tried yet, 1 d_pot allocated, -1 no cache (not eligible, DWX_NO_POT_CACHE, no memory)
   std::vector<uint8_t> pot_valid;   // [launches] one sweep stored every query tile's sum, no weight changed since
@@ -364,6 +371,7 @@ struct dwx_sampler {
     rt::dfree(d_edges); rt::dfree(d_edges8); rt::dfree(d_vifs); rt::dfree(d_assign_free); rt::dfree(d_assign_evid);
     rt::dfree(d_tally); rt::dfree(d_weights); rt::dfree(d_w32); rt::dfree(d_w_init); rt::dfree(d_terms); rt::dfree(d_delta);
     rt::dfree(d_pot); rt::dfree(d_rb); rt::dfree(d_trace); rt::dfree(d_w32_prev);
+    rt::dfree(d_frecs); rt::dfree(d_fvifs); rt::dfree(d_ffval64); rt::dfree(d_fwide);
     rt::dfree(d_w_fixed); rt::dfree(d_grad); rt::dfree(d_persist_rows); rt::dfree(d_persist_bar);
     rt::dfree(d_gbuf[1]); rt::dfree(d_gbuf[2]); rt::dfree(d_wbuf64[0]); rt::dfree(d_wbuf64[1]); rt::dfree(d_wbuf32[0]); rt::dfree(d_wbuf32[1]);
     for (int i = 0; i < 2; ++i) { if (side[i]) rt::stream_destroy(side[i]); if (ev_join[i]) rt::event_destroy(ev_join[i]); }
@@ -1545,6 +1553,7 @@ int dwx_graph_get_info(const dwx_graph *g, dwx_graph_info *out) {
   out->max_super_tile_variables = 0;
   for (const SuperTile &st : c.supers) out->max_super_tile_variables = std::max<uint64_t>(out->max_super_tile_variables, st.nv);
   out->grad_shift = c.grad_shift; out->grad_unit_max = c.grad_unit_max; out->max_records_per_weight = c.max_records_per_weight;
+  out->factor_table_bytes = c.factor_table_bytes();
   return DWX_OK;
 }
 
@@ -2487,6 +2496,141 @@ int dwx_trace_cooccurrence(dwx_sampler *s, const uint64_t *rows_a, const uint64_
   uint64_t *outs[3] = {n_ab, n_a, n_b};
   for (int k = 0; k < 3; ++k)
     if (outs[k]) std::copy(counts.data() + k * n_pairs, counts.data() + (k + 1) * n_pairs, outs[k]);
+  return DWX_OK;
+}
+
+namespace {
+// dwx_score / dwx_trace_score: the device copy of the graph's factor-major table, uploaded by the first call.
+// *nomem: the device has no room (nothing is kept, the sampler stays usable).
+void ensure_score_table(dwx_sampler *s, bool *nomem) {
+  if (s->score_ready) return;
+  const CompiledGraph &c = *s->cg;
+  void *p[4] = {nullptr, nullptr, nullptr, nullptr};
+  const void *h[4] = {c.frecs.data(), c.fvifs.data(), c.ffval64.data(), c.fwide.data()};
+  const size_t bytes[4] = {c.frecs.size() * sizeof(FactorRec), c.fvifs.size() * sizeof(VifRec), c.ffval64.size() * 8,
+                           c.fwide.size() * 4};
+  try {
+    for (int i = 0; i < 4; ++i) {
+      if (!bytes[i]) continue;
+      p[i] = optional_dmalloc(bytes[i]);
+      if (!p[i]) {
+        for (int k = 0; k < 4; ++k) rt::dfree(p[k]);
+        *nomem = true;
+        return;
+      }
+      rt::h2d(p[i], h[i], bytes[i], s->stream);
+    }
+    rt::stream_sync(s->stream);
+  } catch (...) {
+    for (int k = 0; k < 4; ++k) rt::dfree(p[k]);
+    throw;
+  }
+  s->d_frecs = (FactorRec *)p[0]; s->d_fvifs = (VifRec *)p[1]; s->d_ffval64 = (double *)p[2]; s->d_fwide = (uint32_t *)p[3];
+  s->score_ready = true;
+}
+
+// The scores of n states into out[n] (staged by the caller: an error leaves its arrays as they were).  mode 0: the
+// one state src = a chain's assignments; mode 1 / 8: entries of the ring, the first in plane slot0.  Passes of
+// SCORE_EB entries, each a launch over the table and one over the wide factors.  -> 0, DWX_E_NOMEM or DWX_E_LIMIT.
+int run_score(dwx_sampler *s, int mode, const void *src, uint32_t slot0, uint64_t n, double *out) {
+  const CompiledGraph &c = *s->cg;
+  if (!c.F) { std::fill(out, out + n, 0.0); return DWX_OK; }
+  bool nomem = false;
+  ensure_score_table(s, &nomem);
+  if (nomem) return DWX_E_NOMEM;
+  std::vector<unsigned long long> acc(2 * n + 1);
+  unsigned long long *d_acc = (unsigned long long *)optional_dmalloc(acc.size() * 8);
+  if (!d_acc) return DWX_E_NOMEM;
+  try {
+    rt::dmemset(d_acc, 0, acc.size() * 8, s->stream);
+    const uint32_t F = (uint32_t)c.F, n_wide = (uint32_t)c.fwide.size();
+    const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)F + BLOCK_THREADS - 1) / BLOCK_THREADS, SCORE_MAX_BLOCKS);
+    const unsigned wgrid = (unsigned)std::min<uint64_t>(((uint64_t)n_wide + 3) / 4, SCORE_MAX_BLOCKS);
+    const uint32_t eb = mode == 0 ? 1u : (uint32_t)SCORE_EB;
+    for (uint64_t e0 = 0; e0 < n; e0 += eb) {
+      const uint32_t ne = (uint32_t)std::min<uint64_t>(eb, n - e0);
+      const uint32_t slot = mode == 0 ? 0u : (uint32_t)(((uint64_t)slot0 + e0) % s->trace_cap);
+      unsigned long long *a = d_acc + 2 * e0;
+      unsigned *flag = (unsigned *)(d_acc + 2 * n);
+      auto go = [&](auto lane_kernel, auto wide_kernel) {
+        rt::launch(lane_kernel, grid, BLOCK_THREADS, 0, s->stream, (const FactorRec *)s->d_frecs, (const double *)s->d_ffval64,
+                   (const VifRec *)s->d_fvifs, F, (const double *)s->d_weights, src, s->trace_words, s->trace_cap, slot, ne, a, flag);
+        if (n_wide)
+          rt::launch(wide_kernel, wgrid, BLOCK_THREADS, 0, s->stream, (const FactorRec *)s->d_frecs, (const double *)s->d_ffval64,
+                     (const VifRec *)s->d_fvifs, (const uint32_t *)s->d_fwide, n_wide, (const double *)s->d_weights, src,
+                     s->trace_words, s->trace_cap, slot, ne, a, flag);
+      };
+      if (mode == 0) go(score_kernel<0, 1>, score_wide_kernel<0, 1>);
+      else if (mode == 1) go(score_kernel<1, SCORE_EB>, score_wide_kernel<1, SCORE_EB>);
+      else go(score_kernel<8, SCORE_EB>, score_wide_kernel<8, SCORE_EB>);
+    }
+    rt::d2h(acc.data(), d_acc, acc.size() * 8, s->stream);
+    rt::stream_sync(s->stream);
+  } catch (...) {
+    rt::dfree(d_acc);
+    throw;
+  }
+  rt::dfree(d_acc);
+  if ((uint32_t)acc[2 * n]) return DWX_E_LIMIT;
+  for (uint64_t e = 0; e < n; ++e) {
+    // one correctly rounded conversion of the exact integer sum, then an exact scaling
+    const __int128 total = (__int128)(long long)acc[2 * e] * ((__int128)1 << 32) + (__int128)acc[2 * e + 1];
+    out[e] = (double)total * (1.0 / 4294967296.0);
+  }
+  return DWX_OK;
+}
+
+int score_error(int rc) {
+  if (rc == DWX_E_NOMEM) return fail(rc, "no device memory for the factor table (dwx_graph_info: factor_table_bytes) or the sums of the call");
+  return fail(rc, "a term w * (sign * feature value) of the score is not finite or reaches 2^30: outside the sums' domain");
+}
+}  // namespace
+
+int dwx_score(dwx_sampler *s, int chain, double *score) {
+  if (!s || !score) return fail(DWX_E_INVALID, "null argument");
+  if (!s->cg->keep_factors) return fail(DWX_E_INVALID, "the graph was compiled without dwx_compile_opts.keep_factors");
+  if (chain != 0 && chain != 1) return fail(DWX_E_INVALID, "chain must be 0 (free) or 1 (evidence)");
+  double v = 0.0;
+  int code = DWX_OK;
+  int rc = guarded([&]() {
+    rt::set_device(s->device);
+    flush_pending(s, chain == 0 ? 1 : 2);
+    code = run_score(s, 0, chain == 0 ? s->d_assign_free : s->d_assign_evid, 0u, 1, &v);
+  });
+  if (rc != DWX_OK) return rc;
+  if (code != DWX_OK) return score_error(code);
+  *score = v;
+  return DWX_OK;
+}
+
+int dwx_trace_score(dwx_sampler *s, uint64_t first_entry, uint64_t n_entries, double *scores, uint64_t *best_entry) {
+  if (!s) return fail(DWX_E_INVALID, "null sampler");
+  const CompiledGraph &c = *s->cg;
+  if (!c.keep_factors) return fail(DWX_E_INVALID, "the graph was compiled without dwx_compile_opts.keep_factors");
+  if (!s->d_trace) return fail(DWX_E_INVALID, "the sample trace was never enabled (dwx_trace_enable)");
+  if (c.Vo != c.V) return fail(DWX_E_INVALID, "ghost variables are not traced: a shard's trace holds no joint state to score");
+  if (first_entry > s->trace_count || n_entries > s->trace_count - first_entry)
+    return fail(DWX_E_INVALID, "entries outside the sample trace (dwx_trace_info: count)");
+  if (!n_entries) {
+    if (best_entry) *best_entry = ~0ull;
+    return DWX_OK;
+  }
+  if (!scores) return fail(DWX_E_INVALID, "null argument");
+  std::vector<double> v;
+  int code = DWX_OK;
+  int rc = guarded([&]() {
+    v.resize(n_entries);
+    rt::set_device(s->device);
+    const uint32_t slot0 = (uint32_t)(((uint64_t)s->trace_next + s->trace_cap - s->trace_count + first_entry) % s->trace_cap);
+    code = run_score(s, (int)s->trace_bits, s->d_trace, slot0, n_entries, v.data());
+  });
+  if (rc != DWX_OK) return rc;
+  if (code != DWX_OK) return score_error(code);
+  uint64_t best = 0;
+  for (uint64_t e = 1; e < n_entries; ++e)
+    if (v[e] > v[best]) best = e;           // (strictly: the oldest on a tie)
+  std::copy(v.begin(), v.end(), scores);
+  if (best_entry) *best_entry = first_entry + best;
   return DWX_OK;
 }
 

@@ -631,6 +631,60 @@ void compile_graph(const dwx_graph_desc &d, const dwx_compile_opts &o, CompiledG
     });
 
     phase("vifs");
+    // ---- factor-major table (keep_factors): every factor once, its entries in its own edge order ----
+    g.keep_factors = o.keep_factors != 0;
+    if (g.keep_factors) {
+      const uint32_t T = std::max(1u, nth);
+      auto inline_unary = [&](uint64_t f) {
+        const uint64_t lo = d.fac_edge_offset[f];
+        return d.fac_edge_offset[f + 1] - lo == 1 && edge_dense[lo] <= FREC_ARITY_MAX;
+      };
+      std::vector<uint64_t> part(T + 1, 0);
+      std::vector<std::vector<uint32_t>> wide(T);
+      std::atomic<bool> f64{false};
+      parallel_parts(F, T, [&](uint32_t t, uint64_t fb, uint64_t fe) {
+        uint64_t n = 0;
+        bool any64 = false;
+        for (uint64_t f = fb; f < fe; ++f) {
+          const uint64_t a = d.fac_edge_offset[f + 1] - d.fac_edge_offset[f];
+          if (a > FREC_ARITY_MAX) throw LimitError("factor arity exceeds the factor table's 24-bit field");
+          if (!inline_unary(f)) n += a;
+          if (a > SCORE_WAVE_ARITY) wide[t].push_back((uint32_t)f);
+          any64 = any64 || !((double)(float)d.fac_feature_value[f] == d.fac_feature_value[f]);
+        }
+        part[t + 1] = n;
+        if (any64) f64 = true;
+      });
+      for (uint32_t t = 0; t < T; ++t) part[t + 1] += part[t];
+      if (part[T] >= kUnset) throw LimitError("the factor table's entries exceed 2^32-1");
+      for (auto &w : wide) g.fwide.insert(g.fwide.end(), w.begin(), w.end());
+      g.frecs.reset(F);
+      g.fvifs.reset(part[T]);
+      if (f64) g.ffval64.reset(F);
+      parallel_parts(F, T, [&](uint32_t t, uint64_t fb, uint64_t fe) {
+        uint64_t n = part[t];
+        for (uint64_t f = fb; f < fe; ++f) {
+          const uint64_t lo = d.fac_edge_offset[f], a = d.fac_edge_offset[f + 1] - lo;
+          FactorRec r;
+          r.wid = (uint32_t)d.fac_weight_id[f];
+          r.packed = (uint32_t)d.fac_func[f];
+          const double fv = d.fac_feature_value[f];
+          r.fval = (float)fv;
+          if (!((double)r.fval == fv)) r.packed |= FREC_F64_FLAG;
+          if (f64) g.ffval64[f] = fv;
+          if (inline_unary(f)) {
+            r.packed |= FREC_UNARY | (edge_dense[lo] << FREC_ARITY_SHIFT);
+            r.aux = g.pos[d.edge_vid[lo]];
+          } else {
+            r.packed |= (uint32_t)a << FREC_ARITY_SHIFT;
+            r.aux = (uint32_t)n;
+            for (uint64_t e = lo; e < lo + a; ++e) g.fvifs[n++] = VifRec{g.pos[d.edge_vid[e]], edge_dense[e]};
+          }
+          g.frecs[f] = r;
+        }
+      });
+      phase("factor table");
+    }
     // ---- edge records, variable-major in device order ----
     g.edges.reset(g.NIdx);
     std::atomic<bool> need64{false};

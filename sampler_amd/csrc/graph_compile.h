@@ -86,6 +86,18 @@ struct CompiledGraph {
   std::vector<double> w_init;      // [W]
   std::vector<uint8_t> w_fixed;    // [W]
 
+  // ---- factor-major table (dwx_compile_opts.keep_factors; dwx_score, dwx_trace_score) ----
+  // The layout above is variable-major throughout (a factor sits in every value row that names it, its vif
+  // entries once per record): no reordering of it yields "each factor once", so the option keeps this one.
+  bool keep_factors = false;
+  RawArray<FactorRec> frecs;        // [F] in factor order
+  RawArray<VifRec> fvifs;           // the entries of the factors that are not FREC_UNARY, factor by factor
+  RawArray<double> ffval64;         // [F] or empty: the feature values, where one is not f32-exact
+  std::vector<uint32_t> fwide;      // ascending: factors with arity > SCORE_WAVE_ARITY (a wave each)
+  uint64_t factor_table_bytes() const {
+    return keep_factors ? 16 * (uint64_t)frecs.size() + 8 * (uint64_t)fvifs.size() + 8 * (uint64_t)ffval64.size() + 4 * (uint64_t)fwide.size() : 0;
+  }
+
   uint64_t device_bytes() const;
 };
 

@@ -30,6 +30,7 @@ SYMBOLS = [
     "dwx_get_weights", "dwx_set_weights", "dwx_average_weights_async",
     "dwx_clear_tallies", "dwx_get_tallies", "dwx_rb_enable", "dwx_get_rb_sums",
     "dwx_trace_enable", "dwx_trace_info", "dwx_trace_read", "dwx_trace_diagnostics", "dwx_trace_cooccurrence",
+    "dwx_score", "dwx_trace_score",
     "dwx_get_assignments", "dwx_set_assignments", "dwx_get_sweep", "dwx_set_sweep",
     "dwx_device_buffer", "dwx_halo_create", "dwx_halo_destroy", "dwx_halo_buffer", "dwx_halo_message_bytes", "dwx_halo_pack_async",
     "dwx_halo_unpack_async", "dwx_stream", "dwx_kernel_time", "dwx_kernel_time_reset",
@@ -58,7 +59,7 @@ class CompileOpts(C.Structure):
                 ("wide_min_records", C.c_uint32), ("no_record_vifs", C.c_uint32),
                 ("no_pull_unary", C.c_uint32), ("no_sorted_records", C.c_uint32),
                 ("super_tiles", C.c_uint32), ("sorted_slots", C.c_uint32), ("defer_sorted_records", C.c_uint32),
-                ("no_narrow_info", C.c_uint32)]
+                ("no_narrow_info", C.c_uint32), ("keep_factors", C.c_uint32)]
 
 
 class GraphInfo(C.Structure):
@@ -69,7 +70,7 @@ class GraphInfo(C.Structure):
         ("has_categorical", C.c_uint32), ("order_is_identity", C.c_uint32), ("num_wide_tiles", C.c_uint64),
         ("num_staged_tiles", C.c_uint64), ("num_super_tiles", C.c_uint64), ("num_sorted_records", C.c_uint64),
         ("grad_shift", C.c_uint64), ("grad_unit_max", C.c_uint64), ("max_records_per_weight", C.c_uint64),
-        ("max_super_tile_variables", C.c_uint64)]
+        ("max_super_tile_variables", C.c_uint64), ("factor_table_bytes", C.c_uint64)]
 
 
 # TileDesc::flags (sampler_amd/csrc/device_types.h)
@@ -143,6 +144,8 @@ class Library:
         L.dwx_trace_read.argtypes = [vp, u64, u64, vp, u64, vp]
         L.dwx_trace_diagnostics.argtypes = [vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
         L.dwx_trace_cooccurrence.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp, vp]
+        L.dwx_score.argtypes = [vp, i32, vp]
+        L.dwx_trace_score.argtypes = [vp, u64, u64, vp, vp]
         L.dwx_get_assignments.argtypes = [vp, i32, vp]
         L.dwx_set_assignments.argtypes = [vp, i32, vp]
         L.dwx_get_sweep.argtypes = [vp, vp]; L.dwx_set_sweep.argtypes = [vp, u64]
@@ -482,6 +485,49 @@ class GibbsSampler:
         self.lib.check(self.lib.L.dwx_trace_cooccurrence(self.h, rows_a.ctypes.data, rows_b.ctypes.data, len(rows_a),
                                                          first, n, n_ab.ctypes.data, n_a.ctypes.data, n_b.ctypes.data))
         return n_ab, n_a, n_b, n
+
+    # ---- joint log-score (include/dwx.h: dwx_score states the definition; needs Graph(..., keep_factors=True)) ----
+    def score(self, chain="evid"):
+        """score(x) = sum over all factors of w * (sign * feature value) of a live chain's state, under the
+        current f64 weights: the log of the unnormalised probability, summed exactly on the device."""
+        out = C.c_double(0.0)
+        c = 0 if chain in (0, "free") else 1
+        self.lib.check(self.lib.L.dwx_score(self.h, c, C.addressof(out)))
+        return out.value
+
+    def _trace_scores(self, first=0, last=None):
+        first = int(first)
+        n = (self.trace_info()[0] if last is None else int(last)) - first
+        if first < 0 or n < 0:
+            raise ValueError("entries [first, last): 0 <= first <= last")
+        out = np.zeros(n, np.float64)
+        best = C.c_uint64(0)
+        # (a range outside the entries held is the library's error to report)
+        self.lib.check(self.lib.L.dwx_trace_score(self.h, first, n, out.ctypes.data, C.addressof(best)))
+        return out, (int(best.value) if n else None)
+
+    def trace_scores(self, first=0, last=None):
+        """float64[last - first]: the score of the trace's entries [first, last) (0 = oldest; default: all held),
+        under the current weights (dwx_trace_score)."""
+        return self._trace_scores(first, last)[0]
+
+    def trace_best(self):
+        """The MAP estimate among the joint states the trace holds: -> (entry, sweep id, score, uint8[owned
+        variables] assignment) of the entry with the largest score (the oldest on a tie)."""
+        scores, best = self._trace_scores()
+        if best is None:
+            raise ValueError("the trace holds no entry")
+        ids = self.trace_info()[2]
+        x = np.zeros(self.graph.info.num_owned_variables, np.uint8)
+        self.lib.check(self.lib.L.dwx_trace_read(self.h, best, 1, None, 0, x.ctypes.data))
+        return best, int(ids[best]), float(scores[best]), x
+
+    def trace_score_diagnostics(self):
+        """-> (split-R-hat, ESS) of the score series over the entries held (diagnostics.split_rhat / ess of that
+        one chain): the whole-chain convergence check."""
+        from . import diagnostics
+        series = self.trace_scores()[None, :]
+        return float(diagnostics.split_rhat(series)[0]), float(diagnostics.ess(series)[0])
 
     def assignments(self, chain):
         out = np.zeros(self.V, np.uint64)

@@ -314,14 +314,16 @@ int dwx_sgd_finish(dwx_sampler *s);
  * (int32)(G[i] >> shift) in a device buffer of the library (*dev32, *n elements) for the caller's
  * all-reduce -- half the bytes of the int64 vector -- and back, G[i] = (int64)count << shift.
  * Replaces nothing in the reference (its replicas average weights once per epoch,
- * src/dimmwitted.cc:209-216); dwx_wait fails if a sum was not a multiple of 2^shift or did not fit. */
+ * src/dimmwitted.cc:209-216); dwx_wait fails if a sum was not a multiple of 2^shift or its count was not
+ * inside (-2^31, 2^31) -- (-2^15, 2^15) at 16 bits. */
 int dwx_grad_pack32_async(dwx_sampler *s, uint32_t shift, void **dev32, uint64_t *n);
 int dwx_grad_unpack32_async(dwx_sampler *s, uint32_t shift);
 /* The general form: bits = 32 as above, or bits = 16 -- two counts per 32-bit word, word i =
  * c[2i] + 65536 c[2i+1] as arithmetic, *n_words = ceil(W / 2): the all-reduce's 32-bit sums of the
  * words are the packed sums of the counts while every SUMMED count stays inside (-2^15, 2^15), i.e.
  * while (sum over ranks of max_records_per_weight) x grad_unit_max < 2^15 -- a quarter of the int64
- * bytes (config 5a: 2 MB per mini-batch at W = 1 M).  RCCL has no 16-bit integer type, hence words. */
+ * bytes (config 5a: 2 MB per mini-batch at W = 1 M).  RCCL has no 16-bit integer type, hence words.
+ * The check dwx_wait makes covers the packs since the last dwx_wait: it reports their bad sums and starts from 0. */
 int dwx_grad_pack_async(dwx_sampler *s, uint32_t shift, uint32_t bits, void **dev32, uint64_t *n_words);
 int dwx_grad_unpack_async(dwx_sampler *s, uint32_t shift, uint32_t bits);
 

@@ -545,7 +545,8 @@ grad_pack32_kernel(const long long *grad, int *out, uint32_t W, uint32_t shift, 
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < W; i += stride) {
     const long long g = grad[i], v = g >> shift;
-    if ((long long)((unsigned long long)v << shift) != g || v != (long long)(int)v) atomicAdd(bad, 1u);
+    // (inside (-2^31, 2^31), symmetric like the 16-bit form: -2^31 fits an int but not its own negation or a sum)
+    if ((long long)((unsigned long long)v << shift) != g || v <= -2147483648ll || v >= 2147483648ll) atomicAdd(bad, 1u);
     out[i] = (int)v;
   }
 }

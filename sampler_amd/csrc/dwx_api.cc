@@ -2130,6 +2130,7 @@ int dwx_wait(dwx_sampler *s) {
       rt::d2h(&bad, s->d_pack_bad, 4, s->stream);
       rt::stream_sync(s->stream);
       s->pack_check_pending = false;
+      if (bad) rt::dmemset(s->d_pack_bad, 0, 4, s->stream);   // (a later pack reports its own count only)
       if (bad) throw std::runtime_error("dwx_grad_pack_async: " + std::to_string(bad) +
                                         " gradient sums were not multiples of 2^shift or did not fit the count width");
     }

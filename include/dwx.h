@@ -54,7 +54,9 @@ typedef struct dwx_graph_desc {
   const uint64_t *dom_value;
   const double *dom_truthiness;
   const uint16_t *fac_func;        /* FACTOR_FUNCTION_TYPE (src/common.h:35-48)   */
-  const uint64_t *fac_edge_offset; /* [num_factors+1]                             */
+  const uint64_t *fac_edge_offset; /* [num_factors+1]; a factor holds at most 65535 variable
+                                      positions (its arity, duplicates counted; the 16-bit field
+                                      of an edge record) -- DWX_E_LIMIT beyond                */
   const uint64_t *fac_weight_id;
   const double *fac_feature_value; /* finite; |value| <= 65536 on a learnable weight (DWX_E_LIMIT
                                       beyond: gradients are summed in 2^-30 fixed point, int64 --
@@ -77,7 +79,12 @@ typedef struct dwx_compile_opts {
   uint32_t tile_rows;          /* value rows per tile (default 256 bool / 1536 categ.) */
   uint32_t conflict_arity_cap; /* factors wider than this do not constrain the
                                   colouring (Hogwild reads, as in the reference);
-                                  default 256                                          */
+                                  default 256, at most 65535 (the arity limit).  Over a
+                                  wider factor an INFERENCE sweep is still a sequential
+                                  scan where all but one of the factor's variables are
+                                  evidence (and evidence is not sampled); a LEARNING sweep
+                                  is Hogwild on the free chain even then: the free chain
+                                  draws evidence variables too                          */
   uint32_t n_threads;          /* host threads for the build (0 = DWX_HOST_THREADS, else the hardware
                                   concurrency capped at 64 and at twice the cgroup's CPU quota)  */
   uint32_t no_compact_records; /* 1: keep 16-byte records even for all-unary graphs

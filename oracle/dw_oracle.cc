@@ -693,12 +693,21 @@ extern "C" int orc_sched_check_independent(orc_sampler *s, const orc_schedule *s
     for (uint64_t i = sch->launch_off[l]; i < sch->launch_off[l + 1]; ++i) launch_of[sch->order[i]] = l;
   // every owned variable must be scheduled; ghosts (the last Vg ids) must not be
   for (uint64_t v = 0; v < s->V; ++v) if ((launch_of[v] == kInvalid) != (v >= s->V - s->Vg)) return 0;
-  for (const Factor &f : s->factors)
-    for (uint64_t i = 0; i < f.num_vars; ++i)
-      for (uint64_t j = i + 1; j < f.num_vars; ++j) {
-        uint64_t a = s->vifs[f.vif_base + i].vid, b = s->vifs[f.vif_base + j].vid;
-        if (a != b && launch_of[a] != kInvalid && launch_of[a] == launch_of[b]) return 0;
-      }
+  // no launch holds two different variables of one factor (one pass per factor: a factor may have 65535 positions)
+  std::vector<uint64_t> seen(sch->n_launches, kInvalid);   // launch -> the factor's variable met in it
+  std::vector<uint64_t> touched;
+  for (const Factor &f : s->factors) {
+    bool ok = true;
+    touched.clear();
+    for (uint64_t i = 0; i < f.num_vars && ok; ++i) {
+      const uint64_t a = s->vifs[f.vif_base + i].vid, l = launch_of[a];
+      if (l == kInvalid) continue;
+      if (seen[l] == kInvalid) { seen[l] = a; touched.push_back(l); }
+      else ok = seen[l] == a;
+    }
+    for (uint64_t l : touched) seen[l] = kInvalid;
+    if (!ok) return 0;
+  }
   return 1;
 }
 

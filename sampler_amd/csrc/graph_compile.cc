@@ -342,7 +342,7 @@ void compile_graph(const dwx_graph_desc &d, const dwx_compile_opts &o, CompiledG
       for (uint64_t f = fb; f < fe; ++f) {
         uint64_t lo = d.fac_edge_offset[f], hi = d.fac_edge_offset[f + 1];
         if (hi < lo || hi > E) throw std::runtime_error("fac_edge_offset not monotone");
-        if (hi - lo > MAX_ARITY) throw LimitError("factor arity exceeds 2^24-1");
+        if (hi - lo > MAX_ARITY) throw LimitError("factor arity exceeds " + std::to_string(MAX_ARITY));
         conflict = conflict || (hi - lo >= 2 && hi - lo <= arity_cap);
         if (!known_func(d.fac_func[f]))
           throw std::runtime_error("Unsupported FACTOR_FUNCTION_TYPE = " + std::to_string(d.fac_func[f]));

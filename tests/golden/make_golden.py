@@ -328,6 +328,35 @@ def randgraph_goldens():
         print("golden: randgraph_s%d" % seed)
 
 
+def widegraph_goldens():
+    """Two graphs with WIDE factors (tests/wide_factor_cases.py: golden_graph(seed) -- 40 variables, every factor
+    function at arities 4, 5, 8 and 33 around single query variables and over random positions, duplicate variables
+    inside a factor, feature values that are no f32; seed 1 with categorical variables and sparse domain blocks),
+    written by sampler_amd.binary_format, with the reference's `dw gibbs -l 30 -i 50 -t 1 -c 1` output under the flag
+    sets of randgraph_goldens.  Pins the oracle's reference mode at these arities (tests/test_wide_factors.py).  A few
+    tens of KB each."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from sampler_amd import binary_format
+    from wide_factor_cases import GOLDEN_FIXTURES, golden_graph
+    base = ["-l", "30", "-i", "50", "--alpha", "0.01", "--diminish", "0.95", "--reg_param", "0.01", "-t", "1", "-c", "1"]
+    for seed, name in enumerate(GOLDEN_FIXTURES):
+        dst = os.path.join(HERE, name)
+        os.makedirs(dst, exist_ok=True)
+        binary_format.write_graph(golden_graph(seed), dst)
+        with open(os.path.join(dst, "dw-args"), "w") as f:
+            f.write(" ".join(base[:-4]) + "\n")
+        for tag, extra in RANDGRAPH_FLAGS.items():
+            a = base + extra
+            with tempfile.TemporaryDirectory() as out:
+                run_ref(dst, a, out)
+                shutil.copy(os.path.join(out, "inference_result.out.weights.text"), os.path.join(dst, "ref_%s.weights.text" % tag))
+                shutil.copy(os.path.join(out, "inference_result.out.text"), os.path.join(dst, "ref_%s.text" % tag))
+            with open(os.path.join(dst, "ref_%s.args" % tag), "w") as f:
+                f.write(" ".join(a) + "\n")
+        print("golden:", name)
+
+
 def codec_goldens():
     """The reference's text2bin codec fixtures (test/text2bin/: TSV inputs and xxd dumps of
     the expected big-endian bytes) -- data files of the reference's tests."""
@@ -361,3 +390,5 @@ if __name__ == "__main__":
         tied_goldens()
     if "randgraph" in which:
         randgraph_goldens()
+    if "widegraph" in which:
+        widegraph_goldens()

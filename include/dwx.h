@@ -505,6 +505,39 @@ int dwx_trace_cooccurrence(dwx_sampler *s, const uint64_t *rows_a, const uint64_
  * traced).  With neither function ever called nothing is allocated or launched. */
 int dwx_score(dwx_sampler *s, int chain, double *score);
 int dwx_trace_score(dwx_sampler *s, uint64_t first_entry, uint64_t n_entries, double *scores, uint64_t *best_entry);
+/* Per-weight feature sums -- the model's sufficient statistics -- of a state or of a range of traced states, computed
+ * on the device.  The reference has no counterpart: its learning sweep forms the gradient one variable at a time
+ * and never reports the sums.
+ * Definition.  For a joint assignment x,  u_f = sign_f(x) * feature_value_f  (one f64 product, no contraction; sign_f
+ * exactly as in dwx_score: the factor function with no variable proposed) and  q_f = llrint(2^32 * u_f)
+ * (round-to-nearest-even), over ALL factors, those on fixed weights and on evidence variables included.
+ *   dwx_weight_stats        stats[w] = the correctly rounded value of (sum over the factors f on weight w of q_f) / 2^32
+ *                           for a live chain (0 free, 1 evidence); deferred draws are run first, as dwx_score does.
+ *   dwx_trace_weight_stats  sums[w] = the correctly rounded value of (sum over the entries e of [first_entry,
+ *                           first_entry + n_entries) and over the factors f on w of q_f(x_e)) / 2^32, entry 0 the
+ *                           oldest held (as dwx_trace_read).  The caller divides by n_entries for the mean: for the
+ *                           +-1 functions that is 2 * (satisfied fraction) - 1 of the rule under the posterior.
+ * Both arrays have num_weights entries; a weight that no factor names reads 0.0.  The weights' VALUES take no part:
+ * after dwx_set_weights the result is bit for bit the same.  stats(evidence chain) - stats(free chain) is the
+ * one-sample estimate of d log-likelihood / d w.
+ * Numerics.  The per-weight sums are integers and exact: q >> 32 into a signed 64-bit sum, the low 32 bits into an
+ * unsigned one, the result (double)(((__int128)hi << 32) + lo) * 2^-32; it does not depend on the grid, on which lanes
+ * combined their terms before the atomics or on the atomics' order.  A term that is not finite or has |u_f| >= 2^30
+ * makes the call fail with DWX_E_LIMIT.  The two limbs hold fewer than 2^32 terms per weight: the call fails with
+ * DWX_E_LIMIT -- before anything is launched, the error text naming the weight -- when n_entries * (factors on the
+ * most-used weight) >= 2^32 (the count is taken once, when the first of these calls runs); the caller splits the
+ * entry range and adds.  (RATIO at arity >= 3: as for dwx_score.)
+ * Both need a graph compiled with dwx_compile_opts.keep_factors and share the device copy of the factor table with
+ * dwx_score / dwx_trace_score (whichever call comes first uploads it).  Temporary device memory: 16 bytes per weight
+ * (the per-weight factor counts stay on the host); DWX_E_NOMEM leaves the sampler usable.  Both are ordered after
+ * everything queued on the sampler's stream, return when done and change nothing of the sampler's state (sweep
+ * counter, chains, tallies, RB sums, trace, weights, the pack check).  n_entries == 0 is DWX_OK and all zeros; so is a
+ * graph without factors.  After any error return the output array is as it was.
+ * DWX_E_INVALID: the graph was compiled without keep_factors; a null output; a chain other than 0 / 1;
+ * dwx_trace_weight_stats: trace never enabled, a range outside the entries held, a graph with ghost variables (they
+ * are not traced).  With neither function ever called nothing is allocated or launched. */
+int dwx_weight_stats(dwx_sampler *s, int chain, double *stats /* [num_weights] */);
+int dwx_trace_weight_stats(dwx_sampler *s, uint64_t first_entry, uint64_t n_entries, double *sums /* [num_weights] */);
 /* assignments_free (chain 0) / assignments_evid (chain 1), original variable order */
 int dwx_get_assignments(dwx_sampler *s, int chain, uint64_t *out);
 int dwx_set_assignments(dwx_sampler *s, int chain, const uint64_t *in);

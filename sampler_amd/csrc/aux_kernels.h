@@ -978,6 +978,154 @@ score_wide_kernel(const FactorRec *recs, const double *fval64, const VifRec *vif
   score_reduce<EB>(hi, lo, bad, ne, acc, flag);
 }
 
+// dwx_weight_stats / dwx_trace_weight_stats: per weight w the exact sum of u_f = sign_f * fval_f over the factors on
+// w and over the entries [0, n) of the call (include/dwx.h states the definition, DESIGN.md 3.1k the choices): the
+// score's reads without the weights' values, and a scatter onto W hi / lo pairs acc[2w], acc[2w + 1] instead of
+// one pair per entry.  Terms are combined in three steps before any atomic: over the entries inside the lane (the
+// loop over groups of EB entries below: a factor's record, its feature value and wid are read once per call),
+// over neighbouring lanes of equal wid with the keyed segmented sum, and only run heads issue the atomic pair.
+// Integer sums: the result does not depend on the grid, on which lanes combined or on the order of the atomics.
+#ifndef DWX_WSTATS_EB
+#define DWX_WSTATS_EB 8
+#endif
+constexpr int WSTATS_EB = DWX_WSTATS_EB;
+#ifndef DWX_WSTATS_MAX_BLOCKS
+#define DWX_WSTATS_MAX_BLOCKS 2048
+#endif
+constexpr uint32_t WSTATS_MAX_BLOCKS = DWX_WSTATS_MAX_BLOCKS;   // the grid's cap: eight workgroups per CU
+constexpr uint32_t WSTATS_NO_KEY = 0xFFFFFFFFu;                  // an idle lane's key (no weight has this id: W < 2^32)
+
+// the plane of the g-th group of EB entries of a call whose first entry lies in plane slot0 (g * EB < n <= cap)
+DWX_DEV uint32_t wstats_group_slot(uint32_t slot0, uint32_t e0, uint32_t cap) {
+  const uint64_t s = (uint64_t)slot0 + e0;          // (slot0 < cap or a live chain's 0 == cap; e0 < n <= cap: one wrap at the most)
+  return (uint32_t)(s >= cap ? s - cap : s);
+}
+
+// The run of equal keys a lane belongs to, numbered along the wave.  The segmented sum wants equal keys in ONE run
+// of neighbouring lanes (pull_grad_kernel's are sorted); weight ids in factor order are not -- w, x, w would add
+// lane 2 into lane 0 -- so the sums below are keyed by the run's number instead.  A lane learns its right
+// neighbour's key from the pair swap (even lanes) or from a two-lane segmented sum over the pairs (1, 2), (3, 4), ...
+// (odd lanes); the ballot of "my run ends here" counts the runs before a lane.  Every lane of the workgroup calls.
+DWX_DEV uint32_t wstats_run_id(uint32_t key, uint32_t lane) {
+  const uint32_t partner = DWX_PAIR_SWAP_U32(key);
+  bool unused = false;
+  const long long two = DWX_WAVE_SEG_SUM_I64((lane + 1u) >> 1, (long long)key, unused);
+  const bool cont = (lane & 1u) ? (lane < 63u && (uint32_t)(two - (long long)key) == key) : partner == key;
+  const unsigned long long ends = DWX_BALLOT(!cont);
+  return (uint32_t)__builtin_popcountll(ends & ((1ull << lane) - 1ull));
+}
+
+// A LANE OWNS A FACTOR, grid-stride over the table by whole workgroups: the trip count is the same in all lanes
+// (wave operations close every trip); lanes past the table, and lanes whose factor is the wide kernel's, carry a
+// zero term -- the former under the sentinel key, the latter under their own wid, so that they do not cut a run.
+template <int MODE, int EB>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+weight_stats_kernel(const FactorRec *recs, const double *fval64, const VifRec *vifs, uint32_t n_factors, const void *src,
+                    uint32_t words, uint32_t cap, uint32_t slot0, uint32_t n, unsigned long long *acc, unsigned *flag) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  bool bad = false;
+  for (uint64_t f0 = (uint64_t)blockIdx.x * blockDim.x; f0 < n_factors; f0 += stride) {
+    const uint64_t f = f0 + threadIdx.x;
+    const bool valid = f < n_factors;
+    FactorRec r{0u, 0u, 0u, 0.0f};
+    if (valid) r = recs[f];
+    const uint32_t func = r.packed & FREC_FUNC_MASK, field = r.packed >> FREC_ARITY_SHIFT;
+    const uint32_t arity = (r.packed & FREC_UNARY) ? 1u : field;
+    const bool mine = valid && arity <= SCORE_WAVE_ARITY;
+    long long hi = 0;
+    unsigned long long lo = 0;
+    if (mine) {
+      const double fv = (r.packed & FREC_F64_FLAG) ? fval64[f] : (double)r.fval;
+      for (uint32_t e0 = 0; e0 < n; e0 += (uint32_t)EB) {
+        const uint32_t ne = n - e0 < (uint32_t)EB ? n - e0 : (uint32_t)EB;
+        const ScoreReader<MODE, EB> rd(src, words, cap, wstats_group_slot(slot0, e0, cap), ne);
+        uint32_t nb[EB];
+        bool head[EB], s[EB];
+#pragma unroll
+        for (int u = 0; u < EB; ++u) { nb[u] = 0; head[u] = false; }
+        if (r.packed & FREC_UNARY) {
+          rd.sat(VifRec{r.aux, field}, head);
+        } else {
+          const VifRec *v = vifs + r.aux;
+          for (uint32_t i = 0; i + 1u < arity; ++i) {
+            rd.sat(v[i], s);
+#pragma unroll
+            for (int u = 0; u < EB; ++u) nb[u] += s[u] ? 1u : 0u;
+          }
+          if (arity) rd.sat(v[arity - 1u], head);
+        }
+#pragma unroll
+        for (int u = 0; u < EB; ++u)
+          if ((uint32_t)u < ne) score_term(sign_from_counts(func, arity, nb[u], head[u]) * fv, hi, lo, bad);
+      }
+    }
+    const uint32_t key = valid ? r.wid : WSTATS_NO_KEY;
+    const uint32_t run = wstats_run_id(key, lane);
+    bool first = false;
+    const long long h = DWX_WAVE_SEG_SUM_I64(run, hi, first);
+    const long long l = DWX_WAVE_SEG_SUM_I64(run, (long long)lo, first);   // (two's complement: the unsigned sum mod 2^64, which it is below)
+    if (first && valid) {
+      if (h) atomicAdd(&acc[2 * (size_t)key], (unsigned long long)h);
+      if (l) atomicAdd(&acc[2 * (size_t)key + 1], (unsigned long long)l);
+    }
+  }
+  if (bad) atomicAdd(flag, 1u);
+}
+
+// A WAVE OWNS A WIDE FACTOR, as in score_wide_kernel; lane 0 keeps the terms.  Consecutive factors of a wave's walk
+// that share a weight are combined in lane 0 before the atomic pair (wide[] ascends: factors of one rule are
+// usually neighbours).
+template <int MODE, int EB>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+weight_stats_wide_kernel(const FactorRec *recs, const double *fval64, const VifRec *vifs, const uint32_t *wide, uint32_t n_wide,
+                         const void *src, uint32_t words, uint32_t cap, uint32_t slot0, uint32_t n, unsigned long long *acc,
+                         unsigned *flag) {
+  const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (BLOCK_THREADS / 64u);
+  bool bad = false;
+  uint32_t cur = WSTATS_NO_KEY;
+  long long hi = 0;
+  unsigned long long lo = 0;
+  for (uint32_t i = blockIdx.x * (BLOCK_THREADS / 64u) + (threadIdx.x >> 6); i < n_wide; i += waves) {
+    const uint32_t f = wide[i];
+    const FactorRec r = recs[f];
+    const uint32_t func = r.packed & FREC_FUNC_MASK, arity = r.packed >> FREC_ARITY_SHIFT;
+    const VifRec *v = vifs + r.aux;
+    const double fv = (r.packed & FREC_F64_FLAG) ? fval64[f] : (double)r.fval;
+    if (lane == 0u && r.wid != cur) {
+      if (hi) atomicAdd(&acc[2 * (size_t)cur], (unsigned long long)hi);
+      if (lo) atomicAdd(&acc[2 * (size_t)cur + 1], lo);
+      cur = r.wid; hi = 0; lo = 0;
+    }
+    for (uint32_t e0 = 0; e0 < n; e0 += (uint32_t)EB) {
+      const uint32_t ne = n - e0 < (uint32_t)EB ? n - e0 : (uint32_t)EB;
+      const ScoreReader<MODE, EB> rd(src, words, cap, wstats_group_slot(slot0, e0, cap), ne);
+      long long cnt[EB];
+      bool s[EB];
+#pragma unroll
+      for (int u = 0; u < EB; ++u) cnt[u] = 0;
+      for (uint32_t j = lane; j < arity; j += 64u) {
+        rd.sat(v[j], s);
+        const long long one = j + 1u == arity ? (1ll << 32) : 1ll;
+#pragma unroll
+        for (int u = 0; u < EB; ++u) cnt[u] += s[u] ? one : 0ll;
+      }
+#pragma unroll
+      for (int u = 0; u < EB; ++u) {
+        bool first = false;
+        const long long c = DWX_WAVE_SEG_SUM_I64(0u, cnt[u], first);
+        if (lane == 0u && (uint32_t)u < ne)
+          score_term(sign_from_counts(func, arity, (uint32_t)c, (c >> 32) != 0) * fv, hi, lo, bad);
+      }
+    }
+  }
+  if (lane == 0u && cur != WSTATS_NO_KEY) {
+    if (hi) atomicAdd(&acc[2 * (size_t)cur], (unsigned long long)hi);
+    if (lo) atomicAdd(&acc[2 * (size_t)cur + 1], lo);
+  }
+  if (bad) atomicAdd(flag, 1u);
+}
+
 // test hook: the raw Philox4x32-10 block function and the two uniforms drawn from it, on the
 // device (Random123 known-answer vectors; tests/test_philox_kat.py)
 __global__ void test_philox_kernel(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,

@@ -45,7 +45,7 @@ const FlagSpec kFlags[] = {
     {"", "gpus", true}, {"", "devices", true}, {"", "comm", true}, {"", "rao_blackwell", false},
     {"", "trace", true}, {"", "trace_vars", true},
     {"", "diagnostics", false}, {"", "diag_max_lag", true}, {"", "diag_rhat", true},
-    {"", "trace_pairs", true}, {"", "trace_score", false}, {"", "map", false},
+    {"", "trace_pairs", true}, {"", "trace_score", false}, {"", "map", false}, {"", "weight_stats", false},
 };
 
 const FlagSpec *find_flag(const std::string &tok) {
@@ -190,6 +190,7 @@ CmdLine parse_cmdline(int argc, const char *const argv[]) {
     else if (n == "trace_pairs") a.trace_pairs = val;
     else if (n == "trace_score") a.trace_score = true;
     else if (n == "map") a.map = true;
+    else if (n == "weight_stats") a.weight_stats = true;
     else if (n == "comm") {
       if (val != "rccl" && val != "host") { ++a.num_errors; err << "PARSE ERROR: Argument: --comm\n             must be rccl or host\n"; }
       a.comm = val;
@@ -210,6 +211,7 @@ CmdLine parse_cmdline(int argc, const char *const argv[]) {
   if (a.diagnostics && (a.diag_max_lag < 1 || a.diag_max_lag > 64)) { ++a.num_errors; err << "PARSE ERROR: Argument: --diag_max_lag\n             must be 1 .. 64\n"; }
   if (a.trace_score && !a.trace) { ++a.num_errors; err << "PARSE ERROR: Argument: --trace_score\n             needs --trace N: the scores are those of the sample trace's entries\n"; }
   if (a.map && !a.trace) { ++a.num_errors; err << "PARSE ERROR: Argument: --map\n             needs --trace N: the best joint state is taken from the sample trace\n"; }
+  if (a.weight_stats && !a.trace) { ++a.num_errors; err << "PARSE ERROR: Argument: --weight_stats\n             needs --trace N: the feature sums are taken over the sample trace's entries\n"; }
   if (!a.trace_pairs.empty() && !a.trace) { ++a.num_errors; err << "PARSE ERROR: Argument: --trace_pairs\n             needs --trace N: the joint counts are taken over the sample trace\n"; }
   // XXX hack of the reference to support two step-size flags (src/cmd_parser.cc:158-160)
   if (a.stepsize == 0.01) a.stepsize = a.stepsize2;
@@ -260,6 +262,7 @@ std::ostream &operator<<(std::ostream &stream, const CmdLine &args) {
       {"trace_pairs", [](std::ostream &o, const CmdLine &a) { o << a.trace_pairs; }, [](const CmdLine &a) { return !a.trace_pairs.empty(); }},
       {"trace_score", [](std::ostream &o, const CmdLine &a) { o << a.trace_score; }, [](const CmdLine &a) { return a.trace_score; }},
       {"map", [](std::ostream &o, const CmdLine &a) { o << a.map; }, [](const CmdLine &a) { return a.map; }},
+      {"weight_stats", [](std::ostream &o, const CmdLine &a) { o << a.weight_stats; }, [](const CmdLine &a) { return a.weight_stats; }},
   };
 #undef DWX_ROW
 #undef DWX_ROW_LIST
@@ -1117,6 +1120,31 @@ void dump_scores_to_file(const std::string &score_path, const std::string &map_p
   }
 }
 
+// --weight_stats: per weight the sum of sign * feature value over its factors and over every entry the ring holds,
+// summed on the device (dwx_trace_weight_stats); n_factors[w]: the factors on weight w, counted by the caller while the
+// loaded factor columns were still there
+void dump_weight_stats_to_file(const std::string &path, const std::vector<uint64_t> &n_factors, dwx_sampler *sampler) {
+  auto ok = [](int rc) { if (rc != DWX_OK) throw std::runtime_error(dwx_last_error()); };
+  uint64_t count = 0;
+  ok(dwx_trace_info(sampler, &count, nullptr, nullptr));
+  const uint64_t W = n_factors.size();
+  std::vector<double> sums(W, 0.0);
+  ok(dwx_trace_weight_stats(sampler, 0, count, sums.data()));
+  std::string s = "# entries=" + std::to_string(count) + "\n";
+  char num[64];
+  for (uint64_t w = 0; w < W; ++w) {
+    append_u64(s, w); s.push_back(' ');
+    append_u64(s, n_factors[w]); s.push_back(' ');
+    snprintf(num, sizeof num, "%.17g", sums[w]);
+    s += num; s.push_back(' ');
+    snprintf(num, sizeof num, "%.17g", count ? sums[w] / (double)count : 0.0);
+    s += num; s.push_back('\n');
+  }
+  std::ofstream f(path, std::ios::binary);
+  f.write(s.data(), (std::streamsize)s.size());
+  if (!f) throw std::runtime_error("cannot write " + path);
+}
+
 // Graph-compile options of a `dw gibbs` run.  Ordering the variables of an all-unary graph by the
 // weight of their first record makes a sweep ~5 % faster and the host-side build
 // much slower -- the records are then gathered in a random order: 10 s of a 42 s run at config 5's
@@ -1133,7 +1161,7 @@ dwx_compile_opts compile_opts_for(const CmdLine &args) {
   // (what the gradient all-reduce may assume about the sums: only runs over several GPUs ask)
   co.no_narrow_info = (args.gpus >= 2 || args.n_datacopy > 1) ? 0u : 1u;
   // (the factor-major table: only runs that score ask)
-  co.keep_factors = (args.trace_score || args.map) ? 1u : 0u;
+  co.keep_factors = (args.trace_score || args.map || args.weight_stats) ? 1u : 0u;
   return co;
 }
 
@@ -1208,6 +1236,12 @@ int gibbs(const CmdLine &args) {
     dwx_compile_opts co = compile_opts_for(args);
     ok(dwx_graph_create(&desc, &co, &graph));
     phase("dwx_graph_create (index, colouring, device layout)");
+    // --weight_stats: the factors on each weight, counted before the columns go
+    std::vector<uint64_t> weight_factors;
+    if (args.weight_stats) {
+      weight_factors.assign(lg.n_weights, 0);
+      for (uint64_t f = 0; f < lg.n_factors; ++f) ++weight_factors[lg.fac_weight_id[f]];
+    }
     // the decoded factor / edge columns (42 GB at config 5's size) are dead once the graph is compiled (it keeps
     // no pointer into them): a helper thread gives them back while the sampler is created -- in 64 MiB steps
     // that take the address-space lock shared (host_parallel.h, unmap_parallel), so the creating thread's own
@@ -1413,6 +1447,14 @@ int gibbs(const CmdLine &args) {
         if (args.map) std::cout << "DUMPING... TEXT    : " << fm << std::endl;
         dump_scores_to_file(fs, fm, lg, sampler, base.data(), sparse.data());
         phase("dump scores");
+      }
+      if (args.weight_stats) {
+        // --weight_stats: "# entries=<n>", then "wid n_factors sum mean" (%.17g) per weight id, ascending: the sum over
+        // the trace's entries of sign * feature value over the weight's factors, and that over n.  No reference counterpart.
+        fn = args.output_folder + "/inference_result.out.weight_stats.text";
+        std::cout << "DUMPING... TEXT    : " << fn << std::endl;
+        dump_weight_stats_to_file(fn, weight_factors, sampler);
+        phase("dump weight stats");
       }
       if (progress) {
         // the reference's closing calibration table (InferenceResult::show_marginal_histogram,

@@ -54,6 +54,8 @@ struct CmdLine {
                                 // trace, counted on the device (dwx_trace_cooccurrence), to <out>/inference_result.out.pairs.text
   bool trace_score = false;     // --trace_score (with --trace): the joint log-score of every entry of the trace, summed on
                                 // the device (dwx_trace_score), to <out>/inference_result.out.score.text
+  bool weight_stats = false;    // --weight_stats (with --trace): per weight the sum of sign * feature value over its factors and
+                                // the trace's entries (dwx_trace_weight_stats), to <out>/inference_result.out.weight_stats.text
   bool map = false;             // --map (with --trace): the entry with the largest score as "vid value" lines, to
                                 // <out>/inference_result.out.map.text
   int num_errors = 0;
@@ -130,6 +132,9 @@ TracePairs load_trace_pairs(const std::string &file, const LoadedGraph &g, const
 // "# entries=<n>" then "vid_a value_a vid_b value_b n_ab n_a n_b" per pair, in input order, over all entries held
 void dump_pairs_to_file(const std::string &path, dwx_sampler *sampler, const TracePairs &pairs);
 
+// --weight_stats (dw_cli.cc): "# entries=<n>", then "wid n_factors sum mean" per weight id, ascending, numbers as %.17g;
+// sum = dwx_trace_weight_stats over all entries held, mean = sum / n, n_factors[w] counted on the host by the caller.
+void dump_weight_stats_to_file(const std::string &path, const std::vector<uint64_t> &n_factors, dwx_sampler *sampler);
 // --trace_score / --map (dw_cli.cc): the scores of all entries held (dwx_trace_score).  score_path (if not empty):
 // "# entries=<n> best_sweep=<id> best_score=<%.17g>", then "sweep_id score" (%.17g) per entry, oldest first.  map_path
 // (if not empty): "vid value" of every variable in the best entry (the oldest on a tie), in id order, values as the

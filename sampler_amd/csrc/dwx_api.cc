@@ -248,6 +248,10 @@ struct dwx_sampler {
   double *d_ffval64 = nullptr;
   uint32_t *d_fwide = nullptr;
   bool score_ready = false;
+  // Per-weight feature sums (dwx_weight_stats, dwx_trace_weight_stats): the factors on the
+  // most-used weight, counted once from the table by the first call (the term-count guard of the two-limb sums)
+  bool wstats_ready = false;
+  uint64_t wstats_max_count = 0, wstats_max_wid = 0;
   long long *d_pot = nullptr;       // [V] fixed-point sums by device position (allocated on first use)
   int pot_alloc = 0;                // 0 not tried yet, 1 d_pot allocated, -1 no cache (not eligible, DWX_NO_POT_CACHE, no memory)
   std::vector<uint8_t> pot_valid;   // [launches] one sweep stored every query tile's sum, no weight changed since
@@ -2632,6 +2636,130 @@ int dwx_trace_score(dwx_sampler *s, uint64_t first_entry, uint64_t n_entries, do
     if (v[e] > v[best]) best = e;           // (strictly: the oldest on a tie)
   std::copy(v.begin(), v.end(), scores);
   if (best_entry) *best_entry = first_entry + best;
+  return DWX_OK;
+}
+
+namespace {
+// a launch of the per-weight sums covers this many entries; 0: the whole range in ONE launch, the kernel loops
+// over the groups of WSTATS_EB entries itself (profiles/r18/README.md has both forms' times)
+#ifndef DWX_WSTATS_PASS_ENTRIES
+#define DWX_WSTATS_PASS_ENTRIES 0
+#endif
+
+// dwx_weight_stats / dwx_trace_weight_stats: sum over n states and over the factors on each weight of sign * fval
+// into out[W] (staged by the caller).  mode / src / slot0 as run_score.  -> 0, DWX_E_NOMEM, or DWX_E_LIMIT with
+// *limit_wid < W: the term-count guard refused (nothing was launched), *limit_wid == W: a term outside the domain.
+int run_weight_stats(dwx_sampler *s, int mode, const void *src, uint32_t slot0, uint64_t n, double *out, uint64_t *limit_wid) {
+  const CompiledGraph &c = *s->cg;
+  std::fill(out, out + c.W, 0.0);
+  *limit_wid = c.W;
+  if (!c.F || !n || !c.W) return DWX_OK;
+  bool nomem = false;
+  ensure_score_table(s, &nomem);
+  if (nomem) return DWX_E_NOMEM;
+  if (!s->wstats_ready) {
+    std::vector<uint32_t> count(c.W, 0u);
+    for (uint64_t f = 0; f < c.F; ++f) ++count[c.frecs[f].wid];
+    const auto m = std::max_element(count.begin(), count.end());
+    s->wstats_max_count = *m;
+    s->wstats_max_wid = (uint64_t)(m - count.begin());
+    s->wstats_ready = true;
+  }
+  // the two-limb sums hold fewer than 2^32 terms per weight (n <= trace capacity < 2^32: the product fits 64 bits)
+  if (n * s->wstats_max_count >= (1ull << 32)) {
+    *limit_wid = s->wstats_max_wid;
+    return DWX_E_LIMIT;
+  }
+  std::vector<unsigned long long> acc(2 * c.W + 1);
+  unsigned long long *d_acc = (unsigned long long *)optional_dmalloc(acc.size() * 8);
+  if (!d_acc) return DWX_E_NOMEM;
+  try {
+    rt::dmemset(d_acc, 0, acc.size() * 8, s->stream);
+    const uint32_t F = (uint32_t)c.F, n_wide = (uint32_t)c.fwide.size();
+    const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)F + BLOCK_THREADS - 1) / BLOCK_THREADS, WSTATS_MAX_BLOCKS);
+    const unsigned wgrid = (unsigned)std::min<uint64_t>(((uint64_t)n_wide + 3) / 4, WSTATS_MAX_BLOCKS);
+    unsigned *flag = (unsigned *)(d_acc + 2 * c.W);
+    const uint64_t pass = (mode == 0 || !DWX_WSTATS_PASS_ENTRIES) ? n : (uint64_t)DWX_WSTATS_PASS_ENTRIES;
+    for (uint64_t e0 = 0; e0 < n; e0 += pass) {
+      const uint32_t ne = (uint32_t)std::min<uint64_t>(pass, n - e0);
+      const uint32_t slot = mode == 0 ? 0u : (uint32_t)(((uint64_t)slot0 + e0) % s->trace_cap);
+      auto go = [&](auto lane_kernel, auto wide_kernel) {
+        rt::launch(lane_kernel, grid, BLOCK_THREADS, 0, s->stream, (const FactorRec *)s->d_frecs, (const double *)s->d_ffval64,
+                   (const VifRec *)s->d_fvifs, F, src, s->trace_words, s->trace_cap, slot, ne, d_acc, flag);
+        if (n_wide)
+          rt::launch(wide_kernel, wgrid, BLOCK_THREADS, 0, s->stream, (const FactorRec *)s->d_frecs, (const double *)s->d_ffval64,
+                     (const VifRec *)s->d_fvifs, (const uint32_t *)s->d_fwide, n_wide, src, s->trace_words, s->trace_cap, slot, ne,
+                     d_acc, flag);
+      };
+      if (mode == 0) go(weight_stats_kernel<0, 1>, weight_stats_wide_kernel<0, 1>);
+      else if (mode == 1) go(weight_stats_kernel<1, WSTATS_EB>, weight_stats_wide_kernel<1, WSTATS_EB>);
+      else go(weight_stats_kernel<8, WSTATS_EB>, weight_stats_wide_kernel<8, WSTATS_EB>);
+    }
+    rt::d2h(acc.data(), d_acc, acc.size() * 8, s->stream);
+    rt::stream_sync(s->stream);
+  } catch (...) {
+    rt::dfree(d_acc);
+    throw;
+  }
+  rt::dfree(d_acc);
+  if ((uint32_t)acc[2 * c.W]) return DWX_E_LIMIT;
+  for (uint64_t w = 0; w < c.W; ++w) {
+    const __int128 total = (__int128)(long long)acc[2 * w] * ((__int128)1 << 32) + (__int128)acc[2 * w + 1];
+    out[w] = (double)total * (1.0 / 4294967296.0);
+  }
+  return DWX_OK;
+}
+
+int weight_stats_error(const dwx_sampler *s, int rc, uint64_t limit_wid) {
+  if (rc == DWX_E_NOMEM)
+    return fail(rc, "no device memory for the factor table (dwx_graph_info: factor_table_bytes) or the sums of the call (16 bytes per weight)");
+  if (limit_wid < s->cg->W)
+    return fail(rc, "weight " + std::to_string(limit_wid) + " has " + std::to_string(s->wstats_max_count) +
+                        " factors: entries x factors reaches 2^32 terms, beyond the exact sums (split the entry range)");
+  return fail(rc, "a term sign * feature value is not finite or reaches 2^30: outside the sums' domain");
+}
+}  // namespace
+
+int dwx_weight_stats(dwx_sampler *s, int chain, double *stats) {
+  if (!s || !stats) return fail(DWX_E_INVALID, "null argument");
+  if (!s->cg->keep_factors) return fail(DWX_E_INVALID, "the graph was compiled without dwx_compile_opts.keep_factors");
+  if (chain != 0 && chain != 1) return fail(DWX_E_INVALID, "chain must be 0 (free) or 1 (evidence)");
+  std::vector<double> v;
+  int code = DWX_OK;
+  uint64_t limit_wid = 0;
+  int rc = guarded([&]() {
+    v.resize(s->cg->W);
+    rt::set_device(s->device);
+    flush_pending(s, chain == 0 ? 1 : 2);
+    code = run_weight_stats(s, 0, chain == 0 ? s->d_assign_free : s->d_assign_evid, 0u, 1, v.data(), &limit_wid);
+  });
+  if (rc != DWX_OK) return rc;
+  if (code != DWX_OK) return weight_stats_error(s, code, limit_wid);
+  std::copy(v.begin(), v.end(), stats);
+  return DWX_OK;
+}
+
+int dwx_trace_weight_stats(dwx_sampler *s, uint64_t first_entry, uint64_t n_entries, double *sums) {
+  if (!s) return fail(DWX_E_INVALID, "null sampler");
+  const CompiledGraph &c = *s->cg;
+  if (!c.keep_factors) return fail(DWX_E_INVALID, "the graph was compiled without dwx_compile_opts.keep_factors");
+  if (!sums) return fail(DWX_E_INVALID, "null argument");
+  if (!s->d_trace) return fail(DWX_E_INVALID, "the sample trace was never enabled (dwx_trace_enable)");
+  if (c.Vo != c.V) return fail(DWX_E_INVALID, "ghost variables are not traced: a shard's trace holds no joint state to evaluate");
+  if (first_entry > s->trace_count || n_entries > s->trace_count - first_entry)
+    return fail(DWX_E_INVALID, "entries outside the sample trace (dwx_trace_info: count)");
+  std::vector<double> v;
+  int code = DWX_OK;
+  uint64_t limit_wid = 0;
+  int rc = guarded([&]() {
+    v.resize(c.W);
+    rt::set_device(s->device);
+    const uint32_t slot0 = (uint32_t)(((uint64_t)s->trace_next + s->trace_cap - s->trace_count + first_entry) % s->trace_cap);
+    code = run_weight_stats(s, (int)s->trace_bits, s->d_trace, slot0, n_entries, v.data(), &limit_wid);
+  });
+  if (rc != DWX_OK) return rc;
+  if (code != DWX_OK) return weight_stats_error(s, code, limit_wid);
+  std::copy(v.begin(), v.end(), sums);
   return DWX_OK;
 }
 

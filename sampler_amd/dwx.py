@@ -30,7 +30,7 @@ SYMBOLS = [
     "dwx_get_weights", "dwx_set_weights", "dwx_average_weights_async",
     "dwx_clear_tallies", "dwx_get_tallies", "dwx_rb_enable", "dwx_get_rb_sums",
     "dwx_trace_enable", "dwx_trace_info", "dwx_trace_read", "dwx_trace_diagnostics", "dwx_trace_cooccurrence",
-    "dwx_score", "dwx_trace_score",
+    "dwx_score", "dwx_trace_score", "dwx_weight_stats", "dwx_trace_weight_stats",
     "dwx_get_assignments", "dwx_set_assignments", "dwx_get_sweep", "dwx_set_sweep",
     "dwx_device_buffer", "dwx_halo_create", "dwx_halo_destroy", "dwx_halo_buffer", "dwx_halo_message_bytes", "dwx_halo_pack_async",
     "dwx_halo_unpack_async", "dwx_stream", "dwx_kernel_time", "dwx_kernel_time_reset",
@@ -146,6 +146,8 @@ class Library:
         L.dwx_trace_cooccurrence.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp, vp]
         L.dwx_score.argtypes = [vp, i32, vp]
         L.dwx_trace_score.argtypes = [vp, u64, u64, vp, vp]
+        L.dwx_weight_stats.argtypes = [vp, i32, vp]
+        L.dwx_trace_weight_stats.argtypes = [vp, u64, u64, vp]
         L.dwx_get_assignments.argtypes = [vp, i32, vp]
         L.dwx_set_assignments.argtypes = [vp, i32, vp]
         L.dwx_get_sweep.argtypes = [vp, vp]; L.dwx_set_sweep.argtypes = [vp, u64]
@@ -528,6 +530,42 @@ class GibbsSampler:
         from . import diagnostics
         series = self.trace_scores()[None, :]
         return float(diagnostics.split_rhat(series)[0]), float(diagnostics.ess(series)[0])
+
+    # ---- per-weight feature sums (include/dwx.h: dwx_weight_stats states the definition; keep_factors=True) ----
+    def weight_stats(self, chain="evid"):
+        """float64[W]: per weight the sum of sign * feature value over its factors in a live chain's state -- the
+        model's sufficient statistic, summed exactly on the device (dwx_weight_stats)."""
+        out = np.zeros(self.W, np.float64)
+        c = 0 if chain in (0, "free") else 1
+        self.lib.check(self.lib.L.dwx_weight_stats(self.h, c, out.ctypes.data))
+        return out
+
+    def trace_weight_stats(self, first=0, last=None):
+        """float64[W]: weight_stats summed over the trace's entries [first, last) (0 = oldest; default: all held),
+        on the device (dwx_trace_weight_stats).  Divide by last - first for the posterior mean."""
+        first = int(first)
+        n = (self.trace_info()[0] if last is None else int(last)) - first
+        if first < 0 or n < 0:
+            raise ValueError("entries [first, last): 0 <= first <= last")
+        out = np.zeros(self.W, np.float64)
+        # (a range outside the entries held is the library's error to report)
+        self.lib.check(self.lib.L.dwx_trace_weight_stats(self.h, first, n, out.ctypes.data))
+        return out
+
+    def trace_feature_means(self):
+        """float64[W]: E_posterior[phi_w] estimated over all entries the trace holds (for the +-1 functions
+        2 * satisfied fraction - 1 of the rule, times its feature value); a weight whose mean never moves is dead."""
+        n = self.trace_info()[0]
+        if not n:
+            raise ValueError("the trace holds no entry")
+        return self.trace_weight_stats() / n
+
+    def likelihood_gradient(self):
+        """float64[W]: weight_stats("evid") - weight_stats("free"), the one-sample estimate of d log-likelihood / d w
+        from the two live chains; 0 where the weight is fixed."""
+        g = self.weight_stats("evid") - self.weight_stats("free")
+        g[np.asarray(self.graph.raw.w_is_fixed) != 0] = 0.0
+        return g
 
     def assignments(self, chain):
         out = np.zeros(self.V, np.uint64)
